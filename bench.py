@@ -10,8 +10,15 @@ iterations are steady-state K-FAC iterations, inverse included at its natural 1/
 rate).  Weak scaling: every GPU runs --envs-per-gpu envs (default 512 = the 8x512
 shard of BASELINE.json configs[3]).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
+
+A plain run sets up, warms up, times the K steps and prints the one JSON line.
+``--dump-outputs DIR`` then writes what the last timed step handed its caller (the
+rollout batch and the updated parameters) as DIR/<name>.npy; the inputs are seeded,
+so two builds run with the same arguments can be compared output for output.
+``--full`` adds the legs that take runs of their own: the CPU baseline of the same
+workload and the nested BASELINE configs[2] line with its CPU leg.
 
 Without torchrun's environment, ``--gpus N > 1`` launches the N ranks itself: the
 parent never touches the GPU, it spawns N fresh interpreters (one per GPU, RANK /
@@ -151,10 +158,17 @@ def parse():
     p.add_argument('--games', choices=['atari57'], default=None,
                    help='atari57: env e plays Atari-57 game e %% 57 (mixed-game batch, BASELINE configs[4]; '
                         'needs --num-actions 18); default: every env synthetic Breakout')
-    p.add_argument('--no-cpu-baseline', action='store_true')
+    p.add_argument('--full', action='store_true',
+                   help='also run the legs beyond the headline figure: the CPU baseline of the same workload '
+                        'and the nested BASELINE configs[2] line with its own CPU leg')
+    p.add_argument('--dump-outputs', metavar='DIR', default=None,
+                   help='after the timed steps, write the last step\'s outputs (rollout batch, updated '
+                        'parameters) as DIR/<name>.npy (float32; large arrays as a fixed seeded sample)')
+    p.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baseline legs')
     p.add_argument('--cpu-iters', type=int, default=3, help='timed CPU-baseline iterations (at most ~20 s)')
     p.add_argument('--no-configs2', action='store_true',
-                   help='skip the nested BASELINE configs[2] line (ACKTR 32 envs x 20 steps) timed after the headline')
+                   help='with --full: skip the nested BASELINE configs[2] line (ACKTR 32 envs x 20 steps) timed '
+                        'after the headline')
     p.add_argument('--configs2-steps', type=int, default=60)
     p.add_argument('--quiet', action='store_true')
     return p.parse_args()
@@ -211,11 +225,33 @@ def main():
     run(args)
 
 
-def _measure(args, N, T, A, algo, games, steps, warmup, prof_site=None, forward_mode=None):
+DUMP_SAMPLE = 1 << 20  # elements kept of an output larger than this (--dump-outputs)
+
+
+def _dump_outputs(path, named):
+    """--dump-outputs: each tensor as <path>/<name>.npy in float32.  An output of more
+    than DUMP_SAMPLE elements is written as its values at DUMP_SAMPLE flat indices drawn
+    from a fixed seed: the same indices in every run, so two runs' samples compare
+    element for element (<name>.npy then has shape [DUMP_SAMPLE])."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, t in named:
+        flat = t.detach().reshape(-1)
+        if flat.numel() > DUMP_SAMPLE:
+            idx = np.random.default_rng(20240607).integers(0, flat.numel(), DUMP_SAMPLE)
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+            arr = flat.to(torch.float32).cpu().numpy()
+        else:
+            arr = flat.to(torch.float32).cpu().numpy().reshape(tuple(t.shape))
+        np.save(os.path.join(path, name + '.npy'), arr)
+
+
+def _measure(args, N, T, A, algo, games, steps, warmup, prof_site=None, forward_mode=None, dump_dir=None):
     """Build the reference training graph for one workload and time `steps`
     iterations after `warmup` (barrier + synchronize on both sides; wall time is
     the max over ranks).  prof_site: the libacmi HIP-event profiling site of the
-    roofline kernel (timed only for the headline workload)."""
+    roofline kernel (timed only for the headline workload).  dump_dir: where rank 0
+    writes the last timed iteration's outputs (_dump_outputs) once the clock stopped."""
     from actorcritic import _lib, parallel
     from actorcritic import session as sess
     from actorcritic.agents import MultiEnvAgent
@@ -258,6 +294,7 @@ def _measure(args, N, T, A, algo, games, steps, warmup, prof_site=None, forward_
                              model.terminals_placeholder: term}, host=False)
         if marks is not None:
             marks[2].record()
+        return obs, act, rew, term, nxt
 
     tot_ms, cnt = ctypes.c_double(), ctypes.c_int()
     with sess.Session(dev) as s:
@@ -283,7 +320,7 @@ def _measure(args, N, T, A, algo, games, steps, warmup, prof_site=None, forward_
             for k in range(steps):
                 th = time.perf_counter()
                 agent.last_sync_wait = 0.0
-                iteration(s, marks[k])
+                batch = iteration(s, marks[k])
                 host.append(time.perf_counter() - th - getattr(agent, 'last_sync_wait', 0.0))
                 inv_flags.append(bool(getattr(optimizer, 'last_flags', (0, 0, 0))[2]) if acktr else False)
             torch.cuda.synchronize()
@@ -297,6 +334,11 @@ def _measure(args, N, T, A, algo, games, steps, warmup, prof_site=None, forward_
             _lib.call('acmi_prof_enable', 0, 0)
         comm_ms, comm_bytes, comm_n = model.engine.comm_collect()
         model.engine.comm_timing(False)
+        if dump_dir and rank == 0 and steps > 0:
+            # what a caller of the timed path holds after its last step: interact()'s
+            # batch and the parameters optimize_op updated in place
+            names = ('observations', 'actions', 'rewards', 'terminals', 'next_observations')
+            _dump_outputs(dump_dir, list(zip(names, batch)) + [('params', model.params)])
     elapsed = parallel.max_over_ranks(elapsed, dev)
     comm_ms_max = parallel.max_over_ranks(comm_ms, dev)
     roll_ms = [m[0].elapsed_time(m[1]) for m in marks]
@@ -342,7 +384,7 @@ def run(args):
     C3 = 32 if acktr else 64
     A = args.num_actions
     r = _measure(args, N, T, A, args.algo, args.games, args.steps, args.warmup, prof_site=_lib.PROF_CONV2_WGRAD,
-                 forward_mode=fwd)
+                 forward_mode=fwd, dump_dir=args.dump_outputs)
     value, ms_per_step = r['value'], r['ms_per_step']
     tot_ms = ctypes.c_double(r['prof_ms'])
     cnt = ctypes.c_int(r['prof_n'])
@@ -352,7 +394,7 @@ def run(args):
     # reference CPU at 1 GPU" target is stated on -- timed by the same clock in the
     # same run, with its SubprocessEnv CPU leg (32 Pipe children)
     c2 = None
-    if (world == 1 and not args.no_configs2
+    if (args.full and world == 1 and not args.no_configs2
             and not (acktr and N == 32 and T == 20 and A == 4 and args.forward == 'f32' and not args.games)):
         c2r = _measure(args, 32, 20, 4, 'acktr', None, args.configs2_steps, max(5, args.warmup),
                        forward_mode=_lib.FWD_F32)
@@ -439,7 +481,7 @@ def run(args):
         roofline['executed_frac_of_16bit_peak'] = nmf * executed / BF16_MFMA_PEAK_TFLOPS
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         # the same workload as the GPU line (envs, steps, algorithm, actions, C3)
         cpu = _cpu_leg(N, T, A, C3, args.algo, args.games, args.cpu_iters)
         if c2 is not None:
@@ -468,7 +510,7 @@ def run(args):
             'allreduce_ms': r['comm_ms'] if world > 1 else 0.0, 'allreduce_bytes': r['comm_bytes'],
             'allreduce_updates_timed': r['comm_n'], 'dist_backend': parallel.backend_name(),
             'roofline': roofline, 'cpu_baseline': cpu,
-            # BASELINE configs[2] on the same clock (null at N > 1 or with --no-configs2)
+            # BASELINE configs[2] on the same clock (--full; null at N > 1 or with --no-configs2)
             'configs2': c2,
         }
         if cpu:

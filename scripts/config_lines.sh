@@ -6,8 +6,8 @@ out="$root/gpurun_out/${1:-lines}"; mkdir -p "$out"
 cd "$root"
 run() {
   local name=$1; shift
-  echo "=== $name: bench.py $*"
-  timeout -k 10 240 python3 bench.py "$@" > "$out/$name.json" 2> "$out/$name.err" || return $?
+  echo "=== $name: bench.py --full $*"
+  timeout -k 10 240 python3 bench.py --full "$@" > "$out/$name.json" 2> "$out/$name.err" || return $?
   tail -1 "$out/$name.json" | cut -c1-260
 }
 run configs3_shard_acktr_512x20 || exit $?

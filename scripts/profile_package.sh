@@ -8,7 +8,7 @@ name=${1:-pkg}
 out="$root/gpurun_out/$name"; mkdir -p "$out"
 cd "$root"
 echo "=== bench"
-timeout -k 10 300 python3 bench.py > "$out/bench_default.json" 2> "$out/bench.err" || exit $?
+timeout -k 10 300 python3 bench.py --full > "$out/bench_default.json" 2> "$out/bench.err" || exit $?
 tail -1 "$out/bench_default.json" | cut -c1-400
 cd /tmp && export TMPDIR=/tmp
 echo "=== rocprofv3 stats"
