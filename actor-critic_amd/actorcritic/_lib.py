@@ -97,6 +97,9 @@ _SIGS = {
     'acmi_a2c_loss_ws_floats': (c_i64, [c_int]),
     'acmi_a2c_loss': (c_int, [c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_float, c_float, c_float,
                               c_vp, c_int, c_vp, c_vp, c_vp]),
+    'acmi_ppo_loss_ws_floats': (c_i64, [c_int]),
+    'acmi_ppo_loss': (c_int, [c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_float, c_float,
+                              c_float, c_float, c_float, c_vp, c_int, c_vp, c_vp, c_vp, c_vp]),
     'acmi_backward_ws_floats': (c_i64, [c_int, c_int, c_int]),
     'acmi_backward': (c_int, [ctypes.POINTER(Net), c_vp, c_i64, c_int, ctypes.POINTER(Acts),
                               ctypes.POINTER(Bwd), c_vp, c_vp, c_vp, c_i64, c_vp]),
@@ -124,6 +127,8 @@ _SIGS = {
     'acmi_momentum_apply': (c_int, [c_vp, c_vp, c_vp, c_i64, c_float, c_float, c_float, c_vp, c_vp, c_vp]),
     'acmi_rmsprop_apply': (c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_float, c_float, c_float, c_float, c_float,
                                    c_vp, c_vp, c_vp]),
+    'acmi_adam_apply': (c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_float, c_float, c_float, c_float, c_float,
+                                c_vp, c_vp, c_vp]),
     'acmi_env_reset': (c_int, [ctypes.POINTER(EnvState), c_int, c_int, c_u32, c_vp, c_i64, c_vp]),
     'acmi_env_step': (c_int, [ctypes.POINTER(EnvState), c_int, c_int, c_u32, c_vp, c_vp, c_i64, c_vp, c_i64,
                               c_vp, c_vp, c_vp, c_i64, c_vp]),

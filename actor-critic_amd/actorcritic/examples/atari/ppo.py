@@ -1,0 +1,112 @@
+"""PPO on Atari — beyond the reference, which stops at A2C / ACKTR.  The structure is
+a2c_acktr.py's: environments -> MultiEnv -> AtariModel -> MultiEnvAgent -> PPOObjective
+-> optimizer -> ``optimize_shared`` -> a session loop that interacts and runs the optimize
+op; checkpoints and summaries are handled the same way.
+
+Defaults are the common Atari PPO setting (Schulman et al. 2017, table 5, at 32 envs):
+conv3 64, 32 envs x 128 steps, 4 epochs x 4 minibatches, clip 0.1, GAE(0.95) with
+batch-normalised advantages, Adam (epsilon 1e-5) at 2.5e-4 decayed linearly to 0, global
+gradient-norm clip 0.5.  Minibatches are env slices (objectives.PPOOptimizeOp).
+"""
+
+import os
+
+import numpy as np
+
+import actorcritic.envs.atari.wrappers as wrappers
+from actorcritic import checkpoint, parallel
+from actorcritic.agents import MultiEnvAgent
+from actorcritic.envs.atari.model import AtariModel
+from actorcritic.examples.atari.a2c_acktr import create_environments, load_model, save_model
+from actorcritic.multi_env import MultiEnv
+from actorcritic.nn import AdamOptimizer, ClipGlobalNormOptimizer, linear_decay
+from actorcritic.objectives import PPOObjective
+from actorcritic.session import Session, get_or_create_global_step, no_op
+
+
+def train_ppo(env_id, num_envs, num_steps, checkpoint_path, model_name, summary_path=None, max_updates=None, seed=0,
+              log_every=10, num_epochs=4, num_minibatches=4, clip_range=0.1, value_clip_range=None):
+    """Trains an Atari model (conv3 64) with PPO.
+
+    ``num_envs`` is per GPU; with WORLD_SIZE > 1 (torchrun) every rank steps its own shard.
+    """
+    parallel.init_from_env()
+    multi_env = MultiEnv(create_environments(env_id, num_envs, seed=seed))
+
+    model = AtariModel(multi_env.observation_space, multi_env.action_space, 64, random_seed=seed)
+    agent = MultiEnvAgent(multi_env, model, num_steps)
+    objective = PPOObjective(model, discount_factor=0.99, entropy_regularization_strength=0.01,
+                             clip_range=clip_range, value_clip_range=value_clip_range, gae_lambda=0.95,
+                             normalize_advantages=True)
+
+    global_step = get_or_create_global_step()
+    # 1e7 env-steps (4e7 frames) over the whole job; global steps = env-steps / batch
+    max_step = 10000000 / (num_envs * num_steps * parallel.world_size())
+    learning_rate = linear_decay(0.00025, 0.0, global_step, max_step, name='learning_rate')
+
+    optimizer = create_optimizer(learning_rate)
+    optimize_op = objective.optimize_shared(optimizer, baseline_loss_weight=0.5, num_epochs=num_epochs,
+                                            num_minibatches=num_minibatches, shuffle_seed=seed,
+                                            global_step=global_step)
+
+    summary_writer = checkpoint.ScalarLog(summary_path) if (summary_path and parallel.rank() == 0) else None
+    summary_op = no_op()
+
+    with Session() as session:
+        load_model(checkpoint_path, model, optimizer, global_step)
+        step = global_step.value
+        updates = 0
+        try:
+            while step < max_step and (max_updates is None or updates < max_updates):
+                observations, actions, rewards, terminals, next_observations, infos = agent.interact(session)
+                episode_rewards = wrappers.EpisodeInfoWrapper.get_episode_rewards_from_info_batch(infos) \
+                    if summary_writer is not None else None
+
+                fetches = [summary_op, global_step, optimize_op]
+                if summary_writer is not None and step % log_every == 0:
+                    fetches += [objective.policy_loss, objective.baseline_loss, objective.mean_entropy,
+                                objective.approx_kl, objective.clip_fraction]
+                out = session.run(fetches, feed_dict={
+                    model.observations_placeholder: observations,
+                    model.bootstrap_observations_placeholder: next_observations,
+                    model.actions_placeholder: actions,
+                    model.rewards_placeholder: rewards,
+                    model.terminals_placeholder: terminals,
+                }, host=len(fetches) > 3)
+                step = global_step.value
+                updates += 1
+                if len(out) > 3:
+                    mean_episode_reward = (np.nan if np.all(np.isnan(episode_rewards))
+                                           else float(np.nanmean(episode_rewards)))
+                    summary_writer.add(step, policy_loss=float(out[3]), baseline_loss=float(out[4]),
+                                       policy_entropy=float(out[5]), approx_kl=float(out[6]),
+                                       clip_fraction=float(out[7]), episode_reward=mean_episode_reward)
+                if step % 100 == 0 and step > 0 and parallel.rank() == 0:
+                    save_model(checkpoint_path, model_name, step, model, optimizer)
+        except KeyboardInterrupt:
+            print('Stop requested')
+            if parallel.rank() == 0:
+                save_model(checkpoint_path, model_name, step, model, optimizer)
+        finally:
+            multi_env.close()
+            if summary_writer is not None:
+                summary_writer.close()
+    return model, optimizer
+
+
+def create_optimizer(learning_rate):
+    """Adam (epsilon 1e-5) + clip .5."""
+    optimizer = AdamOptimizer(learning_rate=learning_rate, epsilon=1e-5)
+    return ClipGlobalNormOptimizer(optimizer, clip_norm=0.5)
+
+
+if __name__ == '__main__':
+    env_id = 'BreakoutNoFrameskip-v4'
+    num_envs = 32
+    num_steps = 128
+    results_path = os.path.abspath('./results')
+    checkpoint_path = results_path + '/checkpoints-ppo/' + env_id
+    summary_path = results_path + '/summaries-ppo/' + env_id
+    os.makedirs(checkpoint_path, exist_ok=True)
+    os.makedirs(summary_path, exist_ok=True)
+    train_ppo(env_id, num_envs, num_steps, checkpoint_path, 'Atari-' + env_id, summary_path)

@@ -3,7 +3,7 @@ the example uses, a2c_acktr.py:233-251).
 
 Every update is: backward through the tower (acmi_backward) -> one all-reduce of the
 gradient buffer when data-parallel -> a fused optimizer kernel
-(acmi_momentum_apply / acmi_rmsprop_apply, global-norm clipping computed on the
+(acmi_momentum_apply / acmi_rmsprop_apply / acmi_adam_apply, global-norm clipping computed on the
 device, no host round trip).
 """
 
@@ -171,6 +171,42 @@ class RMSPropOptimizer(Optimizer):
         _lib.call('acmi_rmsprop_apply', _lib.ptr(eng.params), _lib.ptr(self._ms), _lib.ptr(self._mom),
                   _lib.ptr(grads), eng.params.numel(), self._lr(ctx), self._decay, self._momentum, self._eps,
                   float(clip_norm), _lib.ptr(self._ws), _lib.ptr(self.last_norm), eng.stream())
+
+
+class AdamOptimizer(Optimizer):
+    """TF1 AdamOptimizer (beyond the reference, whose example uses RMSProp / K-FAC):
+    m = b1*m + (1-b1)*g;  v = b2*v + (1-b2)*g^2;  var -= lr_t*m/(sqrt(v)+eps) with
+    lr_t = lr*sqrt(1-b2^t)/(1-b1^t) formed on the host in double.  The step count
+    ``_t`` is a 1-element host tensor, a slot like ``_m`` and ``_v``: checkpoints
+    carry it."""
+
+    def __init__(self, learning_rate, beta1=0.9, beta2=0.999, epsilon=1e-8, use_locking=False, name='Adam'):
+        super().__init__(learning_rate, name)
+        self._beta1, self._beta2, self._eps = float(beta1), float(beta2), float(epsilon)
+        if not (0.0 <= self._beta1 < 1.0 and 0.0 <= self._beta2 < 1.0):
+            raise ValueError('beta1 and beta2 must be in [0, 1)')
+        self._m = self._v = self._t = self._ws = None
+        self.last_norm = None
+
+    _slot_names = ('_m', '_v', '_t')
+
+    def _ensure_slots(self, eng):
+        import torch
+        if self._m is None:
+            self._m = torch.zeros_like(eng.params)
+            self._v = torch.zeros_like(eng.params)
+            self._t = torch.zeros(1, dtype=torch.int64)
+            self._ws = torch.zeros(int(eng.lib.acmi_opt_ws_floats(eng.params.numel())), device=eng.device)
+            self.last_norm = torch.zeros(1, device=eng.device)
+
+    def _apply_dense(self, ctx, eng, grads, clip_norm):
+        self._ensure_slots(eng)
+        self._t += 1
+        t = int(self._t[0])
+        lr_t = self._lr(ctx) * (1.0 - self._beta2 ** t) ** 0.5 / (1.0 - self._beta1 ** t)
+        _lib.call('acmi_adam_apply', _lib.ptr(eng.params), _lib.ptr(self._m), _lib.ptr(self._v), _lib.ptr(grads),
+                  eng.params.numel(), lr_t, self._beta1, self._beta2, self._eps, float(clip_norm),
+                  _lib.ptr(self._ws), _lib.ptr(self.last_norm), eng.stream())
 
 
 class ClipGlobalNormOptimizer(Optimizer):

@@ -15,6 +15,11 @@ exact arithmetic) and ``normalize_advantages`` (batch-normalised advantages for
 the policy loss, acmi_adv_moments / acmi_adv_normalize; under data parallelism
 the moments are summed over ranks, so every rank normalises with the global
 batch's mean and std).
+
+:class:`PPOObjective` (also beyond the reference) shares those targets and
+advantages and replaces the loss by PPO's clipped surrogate (acmi_ppo_loss); its
+``optimize_shared`` op takes several epochs of minibatch gradient steps per
+``session.run`` (:class:`PPOOptimizeOp`).
 """
 
 from abc import ABCMeta, abstractmethod
@@ -235,6 +240,283 @@ class A2CObjective(ActorCriticObjective):
     @property
     def mean_entropy(self):
         return self._mean_entropy
+
+
+def ppo_minibatch_rows(num_envs, num_steps, num_minibatches):
+    """[(first row, rows)] of the ``num_minibatches`` contiguous env slices of an
+    env-major [num_envs][num_steps] batch."""
+    num_envs, num_minibatches = int(num_envs), int(num_minibatches)
+    if num_minibatches < 1 or num_envs % num_minibatches != 0:
+        raise ValueError('num_minibatches ({}) must divide the number of environments ({})'
+                         .format(num_minibatches, num_envs))
+    rows = num_envs // num_minibatches * int(num_steps)
+    return [(j * rows, rows) for j in range(num_minibatches)]
+
+
+def ppo_minibatch_order(shuffle_seed, step, num_epochs, num_minibatches):
+    """The env-slice order of every epoch of one PPO update: a host generator seeded
+    with (shuffle_seed, global step) draws one permutation per epoch."""
+    rng = np.random.default_rng([int(shuffle_seed), int(step)])
+    return [[int(j) for j in rng.permutation(int(num_minibatches))] for _ in range(int(num_epochs))]
+
+
+class _PPORun(object):
+    """What one session.run shares between the PPO nodes."""
+
+    def __init__(self, st, fwd, actions, bufs):
+        self.st, self.fwd, self.actions, self.bufs = st, fwd, actions, bufs
+        self.stepped = False  # the optimize op ran: the scalars are its last step's
+        self.step_st = None
+
+
+class _PPOBuffers(object):
+    def __init__(self, eng, M):
+        z = lambda n: torch.zeros(n, dtype=torch.float32, device=eng.device)
+        self.old_logp, self.old_values = z(M), z(M)
+        self.eval_out = z(5)  # [policy, baseline, entropy, approx kl, clip fraction] without an update
+        self.clip_frac = z(1)  # the gradient steps' clip fraction (their other scalars: UpdateState.loss)
+        self.ws = {}
+
+    def loss_ws(self, eng, M):
+        if M not in self.ws:
+            self.ws[M] = torch.zeros(int(eng.lib.acmi_ppo_loss_ws_floats(M)), dtype=torch.float32,
+                                     device=eng.device)
+        return self.ws[M]
+
+
+class _PPOBatch(Node):
+    """Once per run, from the batch's forward (the rollout's cached activations or a
+    fresh one): old log-probabilities and values, targets and advantages."""
+    name = 'ppo_batch'
+
+    def __init__(self, objective):
+        self.objective = objective
+
+    def _eval(self, ctx):
+        obj = self.objective
+        model = obj._model
+        eng = model.engine
+        st = ctx.eval(obj._targets_node)
+        fwd = st.fwd
+        M = fwd.M
+        actions = _device(ctx.eval(model.actions_placeholder), torch.int32, eng.device).reshape(-1)
+        if actions.numel() != M:
+            raise ValueError('actions must have the shape of the observations batch [env, step]')
+        bufs = obj._buffers.get(M)
+        if bufs is None:
+            bufs = obj._buffers[M] = _PPOBuffers(eng, M)
+        _lib.call('acmi_categorical', _lib.ptr(fwd.flat_logits), eng.A, M, eng.A, _lib.ptr(actions), None,
+                  _lib.ptr(bufs.old_logp), eng.stream())
+        bufs.old_values.copy_(fwd.flat_value)
+        return _PPORun(st, fwd, actions, bufs)
+
+
+class _PPOLoss(Node):
+    """[policy, baseline, entropy, approx_kl, clip_fraction]: of the run's last
+    gradient step when its optimize op ran, else of the whole batch at the current
+    parameters (ratio 1)."""
+    name = 'ppo_losses'
+
+    def __init__(self, objective):
+        self.objective = objective
+
+    def _eval(self, ctx):
+        obj = self.objective
+        run = ctx.eval(obj._batch_node)
+        if not run.stepped:
+            fwd, st, b = run.fwd, run.st, run.bufs
+            obj._launch_loss(fwd, 0, fwd.M, run, st.dhead, b.eval_out[:4], b.eval_out[4:])
+        return run
+
+    def scalars(self, ctx):
+        run = ctx.eval(self)
+        if run.stepped:  # (all-reduced with the gradients: global means)
+            return torch.cat([run.step_st.loss, run.bufs.clip_frac])
+        # no update in the run: this rank's means -- the kernel's 1/world scale undone
+        return run.bufs.eval_out * float(self.objective._model.engine.world_size)
+
+
+class _PPOScalar(Node):
+    def __init__(self, loss_node, index, name):
+        self.loss_node, self.index, self.name = loss_node, index, name
+
+    def _eval(self, ctx):
+        return self.loss_node.scalars(ctx)[self.index]
+
+    def _finalize(self, ctx, value):
+        return self.loss_node.scalars(ctx)[self.index]
+
+
+class PPOObjective(ActorCriticObjective):
+    """PPO's clipped-surrogate objective (Schulman et al. 2017), beyond the reference:
+
+        r = pi(a|s) / pi_old(a|s),  L_pi = -(mean(min(r adv, clip(r, 1-e, 1+e) adv)) + beta mean(H)),
+        L_v = mean((target - V)^2 / 2)   (``value_clip_range``: the clipped form of acmi_ppo_loss)
+
+    with the targets and advantages of :class:`A2CObjective` (n-step or GAE(lambda),
+    optionally batch-normalised) formed once per batch from the policy that collected
+    it.  ``optimize_shared`` returns an op that takes ``num_epochs`` x
+    ``num_minibatches`` gradient steps per ``session.run``.
+    """
+
+    def __init__(self, model, discount_factor=0.99, entropy_regularization_strength=0.01, clip_range=0.1,
+                 value_clip_range=None, gae_lambda=0.95, normalize_advantages=True, advantage_epsilon=1e-8,
+                 name=None):
+        if not float(clip_range) > 0.0:
+            raise ValueError('clip_range must be positive, got {}'.format(clip_range))
+        if value_clip_range is not None and not float(value_clip_range) > 0.0:
+            raise ValueError('value_clip_range must be positive or None, got {}'.format(value_clip_range))
+        if gae_lambda is not None and not 0.0 <= float(gae_lambda) <= 1.0:
+            raise ValueError('gae_lambda must be in [0, 1] or None, got {}'.format(gae_lambda))
+        self._model = model
+        self._gamma = float(discount_factor)
+        self._gae_lambda = None if gae_lambda is None else float(gae_lambda)
+        self._normalize = bool(normalize_advantages)
+        self._adv_eps = float(advantage_epsilon)
+        self._beta = float(entropy_regularization_strength)
+        self._clip = float(clip_range)
+        self._vclip = 0.0 if value_clip_range is None else float(value_clip_range)
+        self._vcoef = 0.5
+        self._name = name or 'PPOObjective'
+        self._table_cache = {}
+        self._buffers = {}
+        self._targets_node = _Targets(self)
+        self._batch_node = _PPOBatch(self)
+        self._loss_node = _PPOLoss(self)
+        self._scalars = {n: _PPOScalar(self._loss_node, i, n) for i, n in enumerate(
+            ('policy_loss', 'baseline_loss', 'mean_entropy', 'approx_kl', 'clip_fraction'))}
+
+    _tables = A2CObjective._tables
+
+    def _launch_loss(self, fwd, row0, rows, run, dhead, loss_out, clip_frac_out):
+        """acmi_ppo_loss of ``fwd`` (a forward of the batch rows row0 .. row0+rows-1)."""
+        eng = self._model.engine
+        b, sl = run.bufs, slice(row0, row0 + rows)
+        _lib.call('acmi_ppo_loss', _lib.ptr(fwd.flat_logits), eng.A, _lib.ptr(fwd.flat_value),
+                  _lib.ptr(run.actions[sl]), _lib.ptr(b.old_logp[sl]), _lib.ptr(b.old_values[sl]),
+                  _lib.ptr(run.st.targets[sl]), _lib.ptr(run.st.adv[sl]), rows, eng.A, self._clip, self._vclip,
+                  self._beta, float(self._vcoef), 1.0 / eng.world_size, _lib.ptr(dhead), eng.ldh,
+                  _lib.ptr(b.loss_ws(eng, rows)), _lib.ptr(loss_out), _lib.ptr(clip_frac_out), eng.stream())
+
+    def optimize_shared(self, optimizer, baseline_loss_weight=0.5, num_epochs=4, num_minibatches=4, shuffle_seed=0,
+                        step_callback=None, global_step=None, **kwargs):
+        """The PPO update op: per ``session.run``, ``num_epochs`` passes over the batch
+        in ``num_minibatches`` gradient steps each (see :class:`PPOOptimizeOp`).
+
+        Minibatches are contiguous ENV slices of the env-major [N][T] batch (so
+        ``num_minibatches`` must divide N: ValueError at run time otherwise); the
+        order of the slices is permuted per epoch, the rows are not shuffled."""
+        from actorcritic.kfac_utils import KfacOptimizer
+        if isinstance(optimizer, KfacOptimizer):
+            raise NotImplementedError('PPOObjective takes first-order optimizers only: K-FAC statistics of the '
+                                      'clipped surrogate are not implemented')
+        if kwargs:
+            raise TypeError('unexpected arguments {}'.format(sorted(kwargs)))
+        if int(num_epochs) < 1 or int(num_minibatches) < 1:
+            raise ValueError('num_epochs and num_minibatches must be at least 1')
+        self._vcoef = float(baseline_loss_weight)
+        return PPOOptimizeOp(self, optimizer, int(num_epochs), int(num_minibatches), int(shuffle_seed),
+                             step_callback, global_step)
+
+    @property
+    def model(self):
+        return self._model
+
+    @property
+    def target_values(self):
+        return _TargetView(self._targets_node, 'targets')
+
+    @property
+    def advantage(self):
+        return _TargetView(self._targets_node, 'adv')
+
+    @property
+    def policy_loss(self):
+        return self._scalars['policy_loss']
+
+    @property
+    def baseline_loss(self):
+        return self._scalars['baseline_loss']
+
+    @property
+    def mean_entropy(self):
+        return self._scalars['mean_entropy']
+
+    @property
+    def approx_kl(self):
+        """mean(log pi_old(a) - log pi(a)) over the rows of the (last) gradient step."""
+        return self._scalars['approx_kl']
+
+    @property
+    def clip_fraction(self):
+        """Share of rows whose ratio left [1 - clip_range, 1 + clip_range]."""
+        return self._scalars['clip_fraction']
+
+
+class PPOOptimizeOp(Node):
+    """One PPO update per ``session.run``:
+
+    1. the batch's forward (the rollout's cached activations, else a fresh one), from
+       it the old log-probabilities / values and -- once -- targets and advantages;
+    2. for every epoch and every env slice, in the epoch's permuted order: the tower
+       on the slice's rows with the current parameters, acmi_ppo_loss, backward,
+       all-reduce, the optimizer's kernel, ``step_callback(epoch, position)``;
+    3. ``global_step`` + 1 (once per run, not per gradient step).
+
+    Env-wise minibatching: a slice is the N / num_minibatches consecutive envs'
+    rows, read in place through pointer offsets; rows are not shuffled individually
+    (that needs a gather ahead of the tower).  ``last_order`` holds the slice order
+    of the last run, ``[epoch][position] -> slice``.  The very first step of a run
+    with one minibatch re-uses the batch's forward.
+    """
+    name = 'ppo_optimize'
+
+    def __init__(self, objective, optimizer, num_epochs, num_minibatches, shuffle_seed, step_callback, global_step):
+        self.objective, self.optimizer = objective, optimizer
+        self.num_epochs, self.num_minibatches, self.shuffle_seed = num_epochs, num_minibatches, shuffle_seed
+        self.step_callback = step_callback
+        self.global_step = global_step
+        self.last_order = None
+        self._runs = 0
+
+    def _eval(self, ctx):
+        from actorcritic.envs.atari.model import ForwardOut
+        obj, opt = self.objective, self.optimizer
+        eng = obj._model.engine
+        run = ctx.eval(obj._batch_node)
+        fwd = run.fwd
+        T = fwd.steps
+        slices = ppo_minibatch_rows(fwd.batch, T, self.num_minibatches)
+        step = self.global_step.value if self.global_step is not None else self._runs
+        order = ppo_minibatch_order(self.shuffle_seed, step, self.num_epochs, self.num_minibatches)
+        st = None
+        for epoch, perm in enumerate(order):
+            for pos, j in enumerate(perm):
+                row0, rows = slices[j]
+                if st is None and self.num_minibatches == 1:
+                    part = fwd  # nothing has changed the parameters since the batch's forward
+                else:
+                    acts = eng.activations(rows, 'ppo')
+                    obs = fwd.obs[row0:row0 + rows]
+                    eng.forward(obs.data_ptr(), rows, acts.struct, want_value=True)
+                    part = ForwardOut(eng, acts, rows // T, T, obs)
+                st = eng.update_state(rows)
+                obj._launch_loss(part, row0, rows, run, st.dhead, st.loss, run.bufs.clip_frac)
+                eng.backward(part, st, with_stats=False)
+                eng.allreduce(st, with_stats=False)
+                opt._apply_dense(ctx, eng, st.grads, 0.0)
+                eng.bump_version()
+                if self.step_callback is not None:
+                    self.step_callback(epoch, pos)
+        if eng.collective:  # (the other four scalars travel with the gradients)
+            from actorcritic import parallel
+            parallel.allreduce_sum_(run.bufs.clip_frac, force=True)
+        run.stepped, run.step_st = True, st
+        self.last_order = order
+        self._runs += 1
+        if self.global_step is not None:
+            self.global_step.assign(self.global_step.value + 1)
+        return None
 
 
 class _TargetView(Node):

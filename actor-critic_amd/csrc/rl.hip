@@ -1,5 +1,5 @@
 // Rollout-side and loss-side kernels: categorical sampling, n-step targets,
-// A2C loss + head gradients, first-order optimizers, batched synthetic Atari
+// A2C and PPO losses + head gradients, first-order optimizers, batched synthetic Atari
 // stepper with the reference's frame-stack / auto-reset / episode-info
 // semantics.  Contracts and reference citations: include/acmi.h.
 #include <math.h>
@@ -235,6 +235,120 @@ __global__ void a2c_loss_final_kernel(const float* part, int nb, int M, float be
 }
 
 // ---------------------------------------------------------------------------
+// PPO clipped-surrogate loss + head gradients (Schulman et al. 2017; beyond the
+// reference).  One thread per row like a2c_loss_kernel, whose log-sum-exp,
+// entropy and gradient expressions are repeated here operation for operation:
+// with old_logp from categorical_kernel on the same logits r is exactly 1 and
+// dhead is a2c_loss_kernel's, bit for bit.
+// ---------------------------------------------------------------------------
+constexpr int PPO_SUMS = 5;  // surrogate, entropy, value loss, old_logp - logp, clipped rows
+
+__global__ void ppo_loss_kernel(const float* logits, int ld, const float* values,
+                                const int32_t* actions, const float* old_logp,
+                                const float* old_values, const float* targets, const float* adv,
+                                int M, int A, float clip_eps, float vclip, float beta,
+                                float vcoef, float gscale, float* dhead, int ldh, float* part) {
+  __shared__ float red[PPO_SUMS][LOSS_BLOCK / 64];
+  const int m = blockIdx.x * blockDim.x + threadIdx.x;
+  float s_pl = 0.f, s_h = 0.f, s_v = 0.f, s_kl = 0.f, s_cf = 0.f;
+  if (m < M) {
+    const float* z = logits + (long long)m * ld;
+    float mx = -INFINITY;
+    for (int a = 0; a < A; ++a) mx = fmaxf(mx, z[a]);
+    float se = 0.f;
+    for (int a = 0; a < A; ++a) se += expf(z[a] - mx);
+    const float lse = mx + logf(se);
+    float H = 0.f;
+    for (int a = 0; a < A; ++a) {
+      const float lp = z[a] - lse;
+      H -= expf(lp) * lp;
+    }
+    const int act = actions[m];
+    const float lpa = z[act] - lse;
+    const float ad = adv[m];
+    const float olp = old_logp[m];
+    const float r = expf(lpa - olp);
+    const float rc = fminf(fmaxf(r, 1.f - clip_eps), 1.f + clip_eps);
+    const float s1 = r * ad, s2 = rc * ad;
+    // the unclipped term is the active minimum (ties: r inside the range, s1 == s2)
+    const bool pol_on = s1 <= s2;
+    s_pl = pol_on ? s1 : s2;
+    s_h = H;
+    s_kl = olp - lpa;
+    s_cf = fabsf(r - 1.f) > clip_eps ? 1.f : 0.f;
+    const float v = values[m], tg = targets[m];
+    const float diff = tg - v;
+    s_v = 0.5f * diff * diff;
+    bool val_on = true;
+    if (vclip > 0.f) {
+      const float vo = old_values[m];
+      const float dv = v - vo;
+      // only a value that left the range can lose its gradient: inside it Vc is V
+      if (fabsf(dv) > vclip) {
+        const float dc = tg - (vo + fminf(fmaxf(dv, -vclip), vclip));
+        const float sc = 0.5f * dc * dc;
+        if (sc > s_v) {
+          s_v = sc;
+          val_on = false;
+        }
+      }
+    }
+    // dL/dz_k = -(1/M)[adv r (onehot_k - p_k) [unclipped] - beta p_k (log p_k + H)]
+    const float w = pol_on ? s1 : 0.f;
+    const float inv = gscale / (float)M;
+    float* g = dhead + (long long)m * ldh;
+    for (int a = 0; a < A; ++a) {
+      const float lp = z[a] - lse;
+      const float p = expf(lp);
+      const float oh = a == act ? 1.f : 0.f;
+      g[a] = -inv * (w * (oh - p) - beta * p * (lp + H));
+    }
+    // d(vcoef * L_v)/dV = vcoef * (V - target) / M where the unclipped square is active
+    const float gv = vcoef * inv * (values[m] - targets[m]);
+    g[A] = val_on ? gv : 0.f;
+    for (int a = A + 1; a < ldh; ++a) g[a] = 0.f;
+  }
+  s_pl = wave_sum(s_pl);
+  s_h = wave_sum(s_h);
+  s_v = wave_sum(s_v);
+  s_kl = wave_sum(s_kl);
+  s_cf = wave_sum(s_cf);
+  const int w = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0) {
+    red[0][w] = s_pl;
+    red[1][w] = s_h;
+    red[2][w] = s_v;
+    red[3][w] = s_kl;
+    red[4][w] = s_cf;
+  }
+  __syncthreads();
+  if (threadIdx.x < PPO_SUMS) {
+    float a = 0.f;
+    for (int i = 0; i < LOSS_BLOCK / 64; ++i) a += red[threadIdx.x][i];
+    part[blockIdx.x * PPO_SUMS + threadIdx.x] = a;
+  }
+}
+
+__global__ void ppo_loss_final_kernel(const float* part, int nb, int M, float beta, float scale,
+                                      float* out, float* clip_frac_out) {
+  // one wave: deterministic fixed-order sums (a2c_loss_final_kernel's order)
+  float s[PPO_SUMS];
+  for (int k = 0; k < PPO_SUMS; ++k) s[k] = 0.f;
+  for (int i = threadIdx.x; i < nb; i += 64)
+    for (int k = 0; k < PPO_SUMS; ++k) s[k] += part[i * PPO_SUMS + k];
+  for (int k = 0; k < PPO_SUMS; ++k) s[k] = wave_sum(s[k]);
+  if (threadIdx.x == 0) {
+    const float mean_pl = s[0] / (float)M;
+    const float mean_h = s[1] / (float)M;
+    out[0] = scale * -(mean_pl + beta * mean_h);
+    out[1] = scale * (s[2] / (float)M);
+    out[2] = scale * mean_h;
+    out[3] = scale * (s[3] / (float)M);
+    if (clip_frac_out) clip_frac_out[0] = scale * (s[4] / (float)M);
+  }
+}
+
+// ---------------------------------------------------------------------------
 // deterministic global sum of squares / dot product (two passes)
 // ---------------------------------------------------------------------------
 constexpr int RED_BLOCKS = 512;
@@ -301,6 +415,21 @@ __global__ void rmsprop_kernel(float* p, float* ms, float* mom, const float* g, 
     const float mo = momentum * mom[i] + lr * gi / sqrtf(m2 + eps);
     mom[i] = mo;
     p[i] -= mo;
+  }
+}
+
+// TF1 AdamOptimizer: lr_t = lr sqrt(1 - b2^t) / (1 - b1^t) comes from the host
+__global__ void adam_kernel(float* p, float* m, float* v, const float* g, long long n, float lr_t,
+                            float beta1, float beta2, float eps, const float* scale) {
+  const float sc = scale[0];
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n;
+       i += (long long)gridDim.x * blockDim.x) {
+    const float gi = g[i] * sc;
+    const float mi = beta1 * m[i] + (1.f - beta1) * gi;
+    const float vi = beta2 * v[i] + (1.f - beta2) * gi * gi;
+    m[i] = mi;
+    v[i] = vi;
+    p[i] -= lr_t * mi / (sqrtf(vi) + eps);
   }
 }
 
@@ -456,6 +585,28 @@ int acmi_a2c_loss(const float* logits, int ld, const float* values, const int32_
   return ACMI_OK;
 }
 
+int64_t acmi_ppo_loss_ws_floats(int M) { return (long long)PPO_SUMS * cdiv(M, LOSS_BLOCK) + 16; }
+
+int acmi_ppo_loss(const float* logits, int ld, const float* values, const int32_t* actions,
+                  const float* old_logp, const float* old_values, const float* targets,
+                  const float* adv, int M, int A, float clip_eps, float vclip, float beta,
+                  float vcoef, float grad_scale, float* dhead, int ldh, float* ws, float* loss_out,
+                  float* clip_frac_out, acmi_stream_t stream) {
+  ACMI_REQUIRE(logits && values && actions && old_logp && targets && adv && dhead && ws &&
+                   loss_out && M > 0 && A >= 1 && ld >= A && ldh >= A + 1 && clip_eps > 0.f &&
+                   (old_values || !(vclip > 0.f)),
+               ACMI_ERR_ARG, "acmi_ppo_loss: bad arguments");
+  const int nb = cdiv(M, LOSS_BLOCK);
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(ppo_loss_kernel, dim3(nb), dim3(LOSS_BLOCK), 0, s, logits, ld, values, actions,
+                     old_logp, old_values, targets, adv, M, A, clip_eps, vclip, beta, vcoef,
+                     grad_scale, dhead, ldh, ws);
+  hipLaunchKernelGGL(ppo_loss_final_kernel, dim3(1), dim3(64), 0, s, ws, nb, M, beta, grad_scale,
+                     loss_out, clip_frac_out);
+  ACMI_LAUNCH_CHECK("acmi_ppo_loss");
+  return ACMI_OK;
+}
+
 int64_t acmi_opt_ws_floats(int64_t n) { (void)n; return RED_BLOCKS + 16; }
 
 static int clip_prologue(const float* g, long long n, float clip_norm, float* ws,
@@ -493,6 +644,20 @@ int acmi_rmsprop_apply(float* params, float* ms, float* mom, const float* grads,
                      0, s, params, ms, mom, grads, (long long)n, lr, decay, momentum, eps,
                      ws + RED_BLOCKS);
   ACMI_LAUNCH_CHECK("acmi_rmsprop_apply");
+  return ACMI_OK;
+}
+
+int acmi_adam_apply(float* params, float* m, float* v, const float* grads, int64_t n, float lr_t,
+                    float beta1, float beta2, float eps, float clip_norm, float* ws,
+                    float* norm_out, acmi_stream_t stream) {
+  ACMI_REQUIRE(params && m && v && grads && ws && n > 0, ACMI_ERR_ARG,
+               "acmi_adam_apply: bad arguments");
+  hipStream_t s = (hipStream_t)stream;
+  int rc = clip_prologue(grads, n, clip_norm, ws, norm_out, s);
+  if (rc) return rc;
+  hipLaunchKernelGGL(adam_kernel, dim3(std::min<long long>(cdiv(n, 256), 2048)), dim3(256), 0, s,
+                     params, m, v, grads, (long long)n, lr_t, beta1, beta2, eps, ws + RED_BLOCKS);
+  ACMI_LAUNCH_CHECK("acmi_adam_apply");
   return ACMI_OK;
 }
 

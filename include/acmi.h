@@ -296,6 +296,37 @@ int acmi_a2c_loss(const float* logits, int ld, const float* values,
                   float* loss_out, acmi_stream_t stream);
 
 /* ------------------------------------------------------------------------
+ * PPO clipped-surrogate losses (Schulman et al. 2017; beyond the reference)
+ * and their gradient w.r.t. the head outputs, in acmi_a2c_loss's layout.
+ * Per row: r = exp(logpi(a) - old_logp),
+ *   s = min(r*adv, clamp(r, 1-clip_eps, 1+clip_eps)*adv),
+ *   L_pi = -(mean(s) + beta*mean(H));
+ *   vclip > 0:  Vc = old_values + clamp(V - old_values, +-vclip),
+ *               L_v = mean(max((V-target)^2, (Vc-target)^2)/2)
+ *   vclip <= 0: L_v = mean((target-V)^2/2)   (old_values may be null).
+ * dhead as acmi_a2c_loss (row stride ldh >= A+1, column A = dL/dV, padding
+ * zero, scaled by grad_scale/M): the policy term of a row is
+ * -(adv*r)(onehot - p) where the unclipped product is the minimum and 0 where
+ * the clipped one is; the entropy term is always there.  dL/dV is
+ * vcoef*(V-target) where the unclipped square is the maximum, else 0.
+ * loss_out[0..3] = grad_scale * (L_pi, L_v, mean entropy,
+ * mean(old_logp - logpi(a)) -- the approximate KL);
+ * clip_frac_out (nullable) [0] = grad_scale * mean(|r-1| > clip_eps).
+ * Deterministic two-pass sums.  The log-sum-exp and logpi(a) are computed
+ * like acmi_categorical's: with old_logp from it on the same logits r == 1.0f
+ * and dhead equals acmi_a2c_loss's bit for bit.
+ * ws: >= acmi_ppo_loss_ws_floats(M) floats.  clip_eps > 0.
+ * ---------------------------------------------------------------------- */
+int64_t acmi_ppo_loss_ws_floats(int M);
+int acmi_ppo_loss(const float* logits, int ld, const float* values,
+                  const int32_t* actions, const float* old_logp,
+                  const float* old_values, const float* targets,
+                  const float* adv, int M, int A, float clip_eps, float vclip,
+                  float beta, float vcoef, float grad_scale, float* dhead,
+                  int ldh, float* ws, float* loss_out, float* clip_frac_out,
+                  acmi_stream_t stream);
+
+/* ------------------------------------------------------------------------
  * Backward through the tower (the rest of tf.gradients, objectives.py:78)
  * fused with the K-FAC input-factor statistics (kfac cov_update_thunks,
  * kfac_utils.py:39,44; registration envs/atari/model.py:219-246):
@@ -456,6 +487,14 @@ int acmi_rmsprop_apply(float* params, float* ms, float* mom,
                        const float* grads, int64_t n, float lr, float decay,
                        float momentum, float eps, float clip_norm, float* ws,
                        float* norm_out, acmi_stream_t stream);
+/* TF1 AdamOptimizer (beyond the reference; the PPO example's optimizer):
+ * m = b1*m + (1-b1)*g;  v = b2*v + (1-b2)*g^2;  var -= lr_t*m/(sqrt(v)+eps),
+ * lr_t = lr*sqrt(1-b2^t)/(1-b1^t) formed by the caller (t = 1, 2, ...).
+ * Clipping, ws and norm_out as above. */
+int acmi_adam_apply(float* params, float* m, float* v, const float* grads,
+                    int64_t n, float lr_t, float beta1, float beta2, float eps,
+                    float clip_norm, float* ws, float* norm_out,
+                    acmi_stream_t stream);
 
 /* ------------------------------------------------------------------------
  * Batched synthetic Atari stepper — replaces MultiEnv.step/reset over
