@@ -112,7 +112,8 @@ _SIGS = {
                                               c_vp, c_vp, c_i64, c_vp]),
     'acmi_debug_ws_flushes': (c_int, []),
     'acmi_debug_convt2': (c_int, [ctypes.POINTER(Net), c_int, c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_vp,
-                                  c_vp]),
+                                  c_vp]),  # mode: 0 two launches (staging), 1 stacked, 2 two launches (resident)
+    'acmi_debug_convt2_form': (c_int, [c_int]),  # -1 by batch size, 0 staging, 1 resident; returns the previous
     'acmi_kfac_ema': (c_int, [c_vp, c_vp, c_vp, c_i64, c_float, c_float, c_float, c_vp]),
     'acmi_kfac_inverse_layout': (c_int, [c_int, c_int, ctypes.POINTER(c_i64), ctypes.POINTER(c_i64)]),
     'acmi_kfac_inverse_floats': (c_i64, [c_int, c_int]),

@@ -356,6 +356,352 @@ void convt2_kernel(const char* prep, const float* __restrict__ d2, const float* 
   }
 }
 
+// The "resident" form of convt2_kernel for large batches: the same tiles, the
+// same k order and the same epilogue arithmetic, but W2^T is copied into LDS
+// ONCE per block and stays there.  The staging form above re-copies the constant
+// 128 KB through its 16 KB ring for every tile (8000 tiles at M = 10240: ~1 GB
+// of L2 reads and LDS writes per launch) with a block barrier per k-step, which
+// ties the four waves of a block to one exposed L2 round trip per k-step.  Here
+//   * one 768-thread block per CU holds the 131,072 B of prepared fragments in
+//     the layout acmi_conv_prepare wrote ([ks][phase][part][lane] x 16 B) plus
+//     2,560 B of epilogue scratch per wave; after the preload's barrier there is
+//     no block-wide barrier until the kernel's end, so waves drift apart;
+//   * the block is three "teams" of four waves, a team being what a block of the
+//     staging form is: team v = 3 blockIdx.x + team takes tiles v, v + G, v + 2G,
+//     ... (G teams in all), so the Gram launch sums the same tiles in the same
+//     order into the same partial slot v as the staging form's block v, and the
+//     store launch publishes max |d1| into the slot tile % 64 of the staging
+//     form's one-tile blocks -- both launches are bit-identical to it;
+//   * the dY fragments are prefetched two to three k-steps ahead in four named
+//     register sets (a k-step's pair of float4 per lane), the two k-steps that
+//     read one 128-byte line of a pixel (channel groups 0, 1 and 2, 3) loaded
+//     together so the second hits the line the first brought in; the four
+//     k-steps of a tap share one pixel pointer, computed once per tap; a tile's
+//     last two k-steps load the first two of the team's next tile;
+//   * a k-step's fragment reads run one phase ahead of its MFMAs;
+//   * the epilogues go through the per-wave scratch in two halves of 16
+//     super-pixel columns: STORE transposes q = 0, 1 then q = 2, 3 ([16][36]
+//     floats), GRAM stages one k16 half at a time ([32 ci][20]: the h = 0, then
+//     h = 1 MFMA order is kept); the teams' final wave-order Gram sums alias it.
+struct CT2R {
+  static constexpr int TEAMS = 3, THREADS = TEAMS * 256, WAVES = THREADS / 64;
+  static constexpr int STORE_LD = 36, GRAM_LD = 20;  // floats per scratch row (conflict-free, 16-B rows)
+  static constexpr int WAVE_SCR = 4 * std::max(16 * STORE_LD, 32 * GRAM_LD);  // 2,560 B
+  static constexpr int LDS_BYTES = CT2::FRAG_BYTES + WAVES * WAVE_SCR;
+  static constexpr int MAX_TEAMS = 768;  // 256 CUs x 3
+};
+static_assert(CT2R::LDS_BYTES <= 163840, "resident W2^T fragments + epilogue scratch exceed a CU's 160 KiB of LDS");
+static_assert(4 * CT2R::WAVE_SCR >= 32 * 32 * 4, "a team's Gram sum red[32][32] aliases its four waves' scratch");
+static_assert(CT2R::WAVE_SCR % 16 == 0 && CT2::FRAG_BYTES % (16 * 64) == 0, "16-byte LDS rows");
+
+// one dY pixel of zeros for the out-of-image taps (weak and writable like
+// gemm_ops.hpp's kMaskRuns, so the compiler cannot fold the loads; nothing writes it)
+__device__ __attribute__((weak, aligned(16))) float kCt2ZeroPixel[CT2::COUT] = {};
+
+template <bool GRAM, bool MASK>
+__global__ __launch_bounds__(CT2R::THREADS)
+void convt2_resident_kernel(const char* prep, const float* __restrict__ d2, const float* __restrict__ a1,
+                            float* __restrict__ d1, int B, float* __restrict__ gpart, const unsigned* d2max,
+                            unsigned* d1max, int G) {
+  __shared__ __attribute__((aligned(16))) char lds[CT2R::LDS_BYTES];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int bwave = __builtin_amdgcn_readfirstlane(tid >> 6);  // wave of the block
+  const int wave = bwave & 3, team = bwave >> 2;               // wave of its team
+  const int J = B * CT2::L;
+  const int ntiles = (J + CT2::TILE - 1) / CT2::TILE;
+  const int v = CT2R::TEAMS * blockIdx.x + team;  // the staging form's block index
+  const bool active = v < G;
+  const int hl = lane >> 5;  // k half of the fragment; row offset 4 of the accumulator
+  const float* zero = zero_run();
+  const float sd = f16x2_scale_of_bits(d2max);
+  const float sw = f16x2_scale_of_bits(reinterpret_cast<const unsigned*>(prep + CT2::FRAG_BYTES));
+  const float inv = 1.f / (sw * sd);
+
+  float d1am = 0.f;  // !GRAM: max |d1| over the lane's stores
+  f32x16 gacc;       // GRAM: this wave's D D^T over its tiles
+#pragma unroll
+  for (int r = 0; r < 16; ++r) gacc[r] = 0.f;
+
+  // super-pixel column of this lane in a tile, and its dY image
+  struct Col {
+    bool ok;
+    int n, Y, X;
+    const float* dimg;
+  };
+  auto col_of = [&](int tile) {
+    Col c;
+    const int j = tile * CT2::TILE + 32 * wave + (lane & 31);
+    c.ok = j < J;
+    const int jj = c.ok ? j : 0;
+    c.n = jj / CT2::L;
+    const int sp = jj - c.n * CT2::L;
+    c.Y = sp / CT2::PW;
+    c.X = sp - c.Y * CT2::PW;
+    c.dimg = d2 + (long long)c.n * (CT2::OH * CT2::OW * CT2::COUT);
+    return c;
+  };
+  // tap t = (a, b) of column c: dY pixel (Y - a, X - b), the lane's channels
+  // 8 hl .. of channel group 0 (k-step 4 t + cg adds 16 cg).  Out-of-image taps
+  // read the zero pixel, selected on the ADDRESS once per tap (no branch: a load
+  // under a branch makes the waitcnt pass drain vmcnt at the join)
+  auto tap_ptr = [&](int t, bool cok, int Y, int X, const float* dimg) {
+    const int a = t >> 1, b = t & 1;
+    const int oy = Y - a, ox = X - b;
+    const bool ok = cok & (oy >= 0) & (oy < CT2::OH) & (ox >= 0) & (ox < CT2::OW);
+    const int oyc = max(oy, 0), oxc = max(ox, 0);  // (in range whenever ok)
+    const float* p = dimg + (oyc * CT2::OW + oxc) * CT2::COUT;
+    return (ok ? p : kCt2ZeroPixel) + 8 * hl;
+  };
+  auto bload = [&](const float* p, int cg, float4 (&x)[2]) {
+    x[0] = *reinterpret_cast<const float4*>(p + 16 * cg);
+    x[1] = *reinterpret_cast<const float4*>(p + 16 * cg + 4);
+  };
+
+  // four B register sets, set ks & 3 for k-step ks (named, never indexed at run
+  // time: a dynamically indexed register array lands in scratch); k-steps 0, 1
+  // of the first tile are in flight across the weight preload
+  float4 bx0[2], bx1[2], bx2[2], bx3[2];
+  Col cur = col_of(min(v, ntiles - 1));
+  const float* pc = tap_ptr(0, cur.ok, cur.Y, cur.X, cur.dimg);
+  bload(pc, 0, bx0);
+  bload(pc, 1, bx1);
+
+  {  // W2^T fragments -> LDS, once: 8192 16-byte runs over 768 threads
+    constexpr int RUNS = CT2::FRAG_BYTES / 16, PER = (RUNS + CT2R::THREADS - 1) / CT2R::THREADS;
+    const uint4* src = reinterpret_cast<const uint4*>(prep);
+    uint4* dst = reinterpret_cast<uint4*>(lds);
+    uint4 r[PER];
+#pragma unroll
+    for (int k = 0; k < PER; ++k) r[k] = src[min(tid + CT2R::THREADS * k, RUNS - 1)];
+#pragma unroll
+    for (int k = 0; k < PER; ++k)
+      if (tid + CT2R::THREADS * k < RUNS) dst[tid + CT2R::THREADS * k] = r[k];
+  }
+  __syncthreads();
+
+  float* scr = reinterpret_cast<float*>(lds + CT2::FRAG_BYTES + bwave * CT2R::WAVE_SCR);
+  const bool amax_per_tile = (G & (kAmaxSlots - 1)) != 0;  // else the team's tiles share a slot
+  auto publish_d1max = [&](int tile) {
+    const float m = wave_max(d1am);
+    if (d1max && lane == 0) {
+      unsigned* q = d1max + kAmaxStride * (tile & (kAmaxSlots - 1));  // (the slot of the staging form's block `tile`)
+      const unsigned u = __float_as_uint(m);
+      if (u > __hip_atomic_load(q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(q, u);
+    }
+  };
+
+  for (int tile = active ? v : ntiles; tile < ntiles; tile += G) {
+    const Col nextc = col_of(min(tile + G, ntiles - 1));
+    const bool jok = cur.ok;
+    const int n = cur.n, Y = cur.Y, X = cur.X;
+
+    f32x16 acc[4];
+#pragma unroll
+    for (int p = 0; p < 4; ++p)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[p][r] = 0.f;
+
+    // k-step on the B set cb with the resident fragments at As, after issuing
+    // `loads` (later k-steps' B sets, into sets that earlier steps have used up)
+    auto step = [&](const char* As, const float4 (&cb)[2], auto&& loads) {
+      loads();
+      __builtin_amdgcn_sched_barrier(0);
+      auto aread = [&](int p, f16x8 (&a)[2]) {
+#pragma unroll
+        for (int q = 0; q < 2; ++q) a[q] = as_f16x8(*reinterpret_cast<const uint4*>(As + (p * 2 + q) * 1024));
+      };
+      f16x8 b[2], a0[2], a1[2];
+      // phase p + 1's fragment reads are issued before phase p's MFMAs (two
+      // fragment sets), phase 0's before the split: no LDS round trip is exposed
+      aread(0, a0);
+      split2x8(cb[0], cb[1], sd, b[0], b[1]);
+      aread(1, a1);
+      acc[0] = mfma_x2(a0, b, acc[0]);
+      aread(2, a0);
+      acc[1] = mfma_x2(a1, b, acc[1]);
+      aread(3, a1);
+      acc[2] = mfma_x2(a0, b, acc[2]);
+      acc[3] = mfma_x2(a1, b, acc[3]);
+      // (the order above, pinned: DS read 0x100, VALU 0x002, MFMA 0x008)
+      __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
+      __builtin_amdgcn_sched_group_barrier(0x002, 64, 0);
+      __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
+      __builtin_amdgcn_sched_group_barrier(0x008, 3, 0);
+      __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
+      __builtin_amdgcn_sched_group_barrier(0x008, 3, 0);
+      __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
+      __builtin_amdgcn_sched_group_barrier(0x008, 6, 0);
+      __builtin_amdgcn_sched_barrier(0);
+    };
+    // one tap (four k-steps) per iteration, not unrolled further (a full unroll
+    // keeps every step's addresses live and spills); the next tap's pointer --
+    // tap 0 of the next tile after the last -- is selected, not branched
+#pragma unroll 1
+    for (int t = 0; t < 4; ++t) {
+      const bool wrap = t == 3;
+      const float* pn = tap_ptr((t + 1) & 3, wrap ? nextc.ok : cur.ok, wrap ? nextc.Y : cur.Y,
+                                wrap ? nextc.X : cur.X, wrap ? nextc.dimg : cur.dimg);
+      const char* As = lds + t * (4 * CT2::STEP_BYTES) + lane * 16;
+      // the two channel groups of a 128-byte line are loaded together: this
+      // tap's groups 2, 3 (sets used up by the last tap), then the next tap's 0, 1
+      step(As, bx0, [&] { bload(pc, 2, bx2); bload(pc, 3, bx3); });
+      step(As + CT2::STEP_BYTES, bx1, [] {});
+      step(As + 2 * CT2::STEP_BYTES, bx2, [&] { bload(pn, 0, bx0); bload(pn, 1, bx1); });
+      step(As + 3 * CT2::STEP_BYTES, bx3, [] {});
+      pc = pn;
+    }
+    cur = nextc;
+#pragma unroll
+    for (int p = 0; p < 4; ++p)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[p][r] *= inv;  // unscale (exact: powers of two)
+
+    // epilogue: rows (phase p, ci) x this wave's 32 super-pixel columns
+    const int half = (lane >> 4) & 1;  // which 16 of the wave's columns this lane's accumulators hold
+    if constexpr (!GRAM) {
+      // as the staging form's (lane (ri = 4 (lane & 7), cj = lane >> 3) stores
+      // channels ri .. ri+3 of super-pixel columns cj + 8 q), the transpose in two
+      // halves: columns 0..15 (q = 0, 1), then 16..31 (q = 2, 3)
+      const int ri = 4 * (lane & 7), cj = lane >> 3;
+      int pix[4];
+      bool qok[4];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int j = tile * CT2::TILE + 32 * wave + cj + 8 * q;
+        qok[q] = j < J;
+        const int jj = qok[q] ? j : 0;
+        const int nn = jj / CT2::L, sp = jj - nn * CT2::L;
+        const int yy = sp / CT2::PW, xx = sp - yy * CT2::PW;
+        pix[q] = (nn * 20 + 2 * yy) * 20 + 2 * xx;
+      }
+#pragma unroll
+      for (int p = 0; p < 4; ++p) {
+        const int dp = (p >> 1) * 20 + (p & 1);
+        uint32_t bits[4];
+        float4 xa[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const int px = pix[q] + dp;
+          if constexpr (MASK) bits[q] = reinterpret_cast<const uint32_t*>(qok[q] ? a1 + px : zero)[0] >> ri;
+          else xa[q] = *reinterpret_cast<const float4*>(qok[q] ? a1 + px * CT2::CIN + ri : zero);
+        }
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+          if (half == h) {
+#pragma unroll
+            for (int g = 0; g < 4; ++g)
+              *reinterpret_cast<float4*>(scr + (lane & 15) * CT2R::STORE_LD + 8 * g + 4 * hl) =
+                  make_float4(acc[p][4 * g], acc[p][4 * g + 1], acc[p][4 * g + 2], acc[p][4 * g + 3]);
+          }
+          __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+          __builtin_amdgcn_wave_barrier();
+          __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+#pragma unroll
+          for (int q = 2 * h; q < 2 * h + 2; ++q) {
+            const float4 x = *reinterpret_cast<const float4*>(scr + (cj + 8 * (q - 2 * h)) * CT2R::STORE_LD + ri);
+            float4 o;
+            if constexpr (MASK) {
+              o.x = (bits[q] & 1u) ? x.x : 0.f;
+              o.y = (bits[q] & 2u) ? x.y : 0.f;
+              o.z = (bits[q] & 4u) ? x.z : 0.f;
+              o.w = (bits[q] & 8u) ? x.w : 0.f;
+            } else {
+              o.x = xa[q].x > 0.f ? x.x : 0.f;
+              o.y = xa[q].y > 0.f ? x.y : 0.f;
+              o.z = xa[q].z > 0.f ? x.z : 0.f;
+              o.w = xa[q].w > 0.f ? x.w : 0.f;
+            }
+            if (qok[q]) {
+              *reinterpret_cast<float4*>(d1 + (long long)(pix[q] + dp) * CT2::CIN + ri) = o;
+              d1am = absmax4(d1am, o);
+            }
+          }
+          __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+          __builtin_amdgcn_wave_barrier();
+          __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        }
+      }
+      if (amax_per_tile) {
+        publish_d1max(tile);
+        d1am = 0.f;
+      }
+    } else {
+#pragma unroll
+      for (int p = 0; p < 4; ++p) {
+        const int py = p >> 1, px = p & 1;
+        const long long pix = ((long long)n * 20 + 2 * Y + py) * 20 + 2 * X + px;
+        // the masked tile in place (rows ci = (r & 3) + 8 (r >> 2) + 4 hl)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+          const int ci = 8 * g + 4 * hl;
+          float4 x;
+          if constexpr (MASK) {  // ReLU' bits: word pix, channels ci .. ci + 3 (zero run past the end)
+            const uint32_t b = *reinterpret_cast<const uint32_t*>(jok ? a1 + pix : zero) >> ci;
+            x = make_float4((float)(b & 1u), (float)((b >> 1) & 1u), (float)((b >> 2) & 1u), (float)((b >> 3) & 1u));
+          } else {
+            x = *reinterpret_cast<const float4*>(jok ? a1 + pix * CT2::CIN + ci : zero);
+          }
+          acc[p][4 * g + 0] = x.x > 0.f ? acc[p][4 * g + 0] : 0.f;
+          acc[p][4 * g + 1] = x.y > 0.f ? acc[p][4 * g + 1] : 0.f;
+          acc[p][4 * g + 2] = x.z > 0.f ? acc[p][4 * g + 2] : 0.f;
+          acc[p][4 * g + 3] = x.w > 0.f ? acc[p][4 * g + 3] : 0.f;
+        }
+        // G += D D^T, k = the 32 super-pixels as two k16 steps, each staged alone
+        // as [ci][16 super-pixels]; the lane's fragment D[ci = lane & 31]
+        // [k = 16 h + 8 hl .. +7] serves as A and as B
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+          if (half == h) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r)
+              scr[((r & 3) + 8 * (r >> 2) + 4 * hl) * CT2R::GRAM_LD + (lane & 15)] = acc[p][r];
+          }
+          __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+          __builtin_amdgcn_wave_barrier();
+          __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+          const float* rp = scr + (lane & 31) * CT2R::GRAM_LD + 8 * hl;
+          const float4 x0 = *reinterpret_cast<const float4*>(rp);
+          const float4 x1 = *reinterpret_cast<const float4*>(rp + 4);
+          uint4 hh, mm, ll;
+          split3(x0.x, x0.y, hh.x, mm.x, ll.x);
+          split3(x0.z, x0.w, hh.y, mm.y, ll.y);
+          split3(x1.x, x1.y, hh.z, mm.z, ll.z);
+          split3(x1.z, x1.w, hh.w, mm.w, ll.w);
+          const bf16x8 f[3] = {__builtin_bit_cast(bf16x8, hh), __builtin_bit_cast(bf16x8, mm),
+                               __builtin_bit_cast(bf16x8, ll)};
+          gacc = mfma_x3(f, f, gacc);
+          __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+          __builtin_amdgcn_wave_barrier();
+          __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        }
+      }
+    }
+  }
+
+  if constexpr (!GRAM) {
+    if (active) publish_d1max(v);  // (every tile of the team has v's slot when not per tile)
+  }
+  __syncthreads();  // every wave is past its epilogues: the Gram sums reuse the scratch
+  if constexpr (GRAM) {
+    // each team's 4 waves' Grams summed in wave order through LDS, then part[v][33][32]
+    float* red = reinterpret_cast<float*>(lds + CT2::FRAG_BYTES + team * 4 * CT2R::WAVE_SCR);  // [32][32]
+    for (int w = 0; w < 4; ++w) {
+      if (wave == w) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const int i = (r & 3) + 8 * (r >> 2) + 4 * hl, jc = lane & 31;
+          red[i * 32 + jc] = (w ? red[i * 32 + jc] : 0.f) + gacc[r];
+        }
+      }
+      __syncthreads();
+    }
+    if (active) {
+      float* out = gpart + (long long)v * 33 * 32;
+      for (int e = tid & 255; e < 32 * 32; e += 256) out[e] = red[e];
+    }
+  }
+}
+
 #ifndef ACMI_CT2_STORE_BLOCKS  // 0: one block per tile; else at most this many blocks (grid-stride)
 #define ACMI_CT2_STORE_BLOCKS 0
 #endif
@@ -367,6 +713,36 @@ inline int convt2_store_blocks(int B) {
 inline int convt2_gram_blocks(int B) {
   const int ntiles = (B * CT2::L + CT2::TILE - 1) / CT2::TILE;
   return std::max(1, std::min(ntiles, 768));
+}
+// the resident form: its teams are the Gram launch's blocks (a multiple of 64 or
+// one tile each: a team's tiles share a max |d1| slot), three to a block
+inline int convt2_resident_teams(int B) { return convt2_gram_blocks(B); }
+inline int convt2_resident_blocks(int B) { return (convt2_resident_teams(B) + CT2R::TEAMS - 1) / CT2R::TEAMS; }
+static_assert(CT2R::MAX_TEAMS == 768 && CT2R::MAX_TEAMS % kAmaxSlots == 0, "teams = convt2_gram_blocks");
+// Fewest tiles (of 128 super-pixel columns: 100 B / 128) at which dx_conv2 takes
+// the resident form, per epilogue.  Below it the 128 KB preload per block and
+// the idle CUs of a short grid cost more than the staging they remove.  Both
+// forms give the same bits; the thresholds affect speed only.
+// Measured per launch at its site in the update (scripts/kbench.py c2mix, one
+// lease, two rounds; us, staging / resident):
+//   B (tiles)      store (loss chain)   Gram (sampled chain)
+//     640 (500)       27.0 /  28.6         24.2 /  26.2
+//    1024 (800)       44.6 /  44.8         38.7 /  42.9
+//    2560 (2000)      85.3 /  69.6         68.2 /  63.6
+//   10240 (8000)     289.2 / 236.3        241.9 / 216.0
+// The crossover lies between 800 and 2000 tiles for both; the thresholds stand
+// at the smallest size measured ahead (profiles/r07_convt2/README.md).
+#ifndef ACMI_CT2R_MIN_TILES_STORE  // (A/B knobs, as ACMI_CT2_STORE_BLOCKS)
+#define ACMI_CT2R_MIN_TILES_STORE 2000
+#endif
+#ifndef ACMI_CT2R_MIN_TILES_GRAM
+#define ACMI_CT2R_MIN_TILES_GRAM 2000
+#endif
+constexpr int kCt2ResidentMinTilesStore = ACMI_CT2R_MIN_TILES_STORE;
+constexpr int kCt2ResidentMinTilesGram = ACMI_CT2R_MIN_TILES_GRAM;
+inline bool convt2_resident_default(int B, bool gram) {
+  const int ntiles = (B * CT2::L + CT2::TILE - 1) / CT2::TILE;
+  return ntiles >= (gram ? kCt2ResidentMinTilesGram : kCt2ResidentMinTilesStore);
 }
 
 }  // namespace acmi

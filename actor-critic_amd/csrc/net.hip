@@ -11,6 +11,7 @@
 #include <stdio.h>
 #include <string.h>
 
+#include <atomic>
 #include <vector>
 
 #include "gemm.hpp"
@@ -1501,6 +1502,14 @@ static int dx_chain_pre(const Layout& L, const float* P, int B, const acmi_acts_
   return ACMI_OK;
 }
 
+// which form of conv2's input gradient dx_conv2 launches (acmi_debug_convt2_form):
+// -1 = by the tile-count thresholds of convt2.hpp, 0 = staging, 1 = resident
+static std::atomic<int> g_convt2_form{-1};
+static bool convt2_use_resident(int B, bool gram) {
+  const int f = g_convt2_form.load(std::memory_order_relaxed);
+  return f < 0 ? convt2_resident_default(B, gram) : f != 0;
+}
+
 // conv2's input gradient, from d2 (max |d2| in dxs): the loss chain stores the
 // masked d1 (gram_part null), the sampled chain reduces it to conv1's G-factor
 // Gram partials (*gram_done set when it did)
@@ -1523,7 +1532,11 @@ static int dx_conv2(const Layout& L, const float* P, int B, const acmi_acts_t* a
       // chain reduces d1 to its Gram partials instead of storing it
       auto go = [&](auto GRAMc, auto MASKc) {
         constexpr bool GR = decltype(GRAMc)::value, MK = decltype(MASKc)::value;
-        if (GR)
+        if (convt2_use_resident(B, GR))  // W2^T resident in LDS (large batches; the same bits)
+          hipLaunchKernelGGL((convt2_resident_kernel<GR, MK>), dim3(convt2_resident_blocks(B)), dim3(CT2R::THREADS),
+                             0, s, p2, bw->d2, act1, GR ? nullptr : bw->d1, B, GR ? gram_part : nullptr,
+                             dxs + kBsMaxD2, GR ? nullptr : dxs + kBsMaxD1, convt2_resident_teams(B));
+        else if (GR)
           hipLaunchKernelGGL((convt2_kernel<GR, MK>), dim3(convt2_gram_blocks(B)), dim3(256), 0, s, p2, bw->d2,
                              act1, nullptr, B, gram_part, dxs + kBsMaxD2, nullptr);
         else
@@ -2270,7 +2283,8 @@ int acmi_debug_convt2(const acmi_net_t* net, int mode, const float* d2a, const f
                       uint32_t* d1max, acmi_stream_t stream) {
   ACMI_REQUIRE(net_modes_ok(net), ACMI_ERR_ARG, "acmi_debug_convt2: bad acmi_net_t mode fields");
   const ModeScope mode_scope(net);
-  ACMI_REQUIRE(net && net->conv_prep && d2a && d2b && m1 && d1 && gram_part && d2max_a && d2max_b && d1max && B > 0,
+  ACMI_REQUIRE(net && net->conv_prep && d2a && d2b && m1 && d1 && gram_part && d2max_a && d2max_b && d1max && B > 0 &&
+                   mode >= 0 && mode <= 2,
                ACMI_ERR_ARG, "acmi_debug_convt2: bad arguments");
   const char* p2 = static_cast<const char*>(net->conv_prep) +
                    (net->conv3_filters == 32 ? TowerPrep<32>::BYTES : TowerPrep<64>::BYTES);
@@ -2281,12 +2295,22 @@ int acmi_debug_convt2(const acmi_net_t* net, int mode, const float* d2a, const f
                        B, nullptr, d2max_a, d1max, nullptr, nullptr);
     hipLaunchKernelGGL((convt2_kernel<true, true>), dim3(convt2_gram_blocks(B)), dim3(256), 0, s, p2, d2b, act1,
                        nullptr, B, gram_part, d2max_b, nullptr, nullptr, nullptr);
-  } else {
+  } else if (mode == 1) {
     hipLaunchKernelGGL((convt2_kernel<true, true, true>), dim3(convt2_gram_blocks(B)), dim3(256), 0, s, p2, d2a,
                        act1, d1, B, gram_part, d2max_a, d1max, d2b, d2max_b);
+  } else {
+    const dim3 grid(convt2_resident_blocks(B)), block(CT2R::THREADS);
+    hipLaunchKernelGGL((convt2_resident_kernel<false, true>), grid, block, 0, s, p2, d2a, act1, d1, B, nullptr,
+                       d2max_a, d1max, convt2_resident_teams(B));
+    hipLaunchKernelGGL((convt2_resident_kernel<true, true>), grid, block, 0, s, p2, d2b, act1, nullptr, B, gram_part,
+                       d2max_b, nullptr, convt2_resident_teams(B));
   }
   ACMI_LAUNCH_CHECK("acmi_debug_convt2");
   return ACMI_OK;
+}
+
+int acmi_debug_convt2_form(int form) {
+  return g_convt2_form.exchange(form < 0 ? -1 : form != 0, std::memory_order_relaxed);
 }
 
 int acmi_debug_ws_flushes(void) {

@@ -640,12 +640,20 @@ int acmi_debug_ws_flushes(void);
  * mode 0 = the two launches of acmi_backward / acmi_kfac_output_stats (the
  * loss chain's d2a -> masked d1 with max |d1| into d1max; the sampled chain's
  * d2b -> conv1's G-factor Gram partials); mode 1 = the same products stacked in
- * one launch (one W2^T stream, the epilogue chosen per tile).  d2max_*: the
- * published max |d2| slots; m1: the ReLU' mask words; needs net->conv_prep. */
+ * one launch (one W2^T stream, the epilogue chosen per tile); mode 2 = the two
+ * launches of mode 0 on the resident form (W2^T held in LDS, one 768-thread
+ * block per CU), whatever the batch size.  All three give the same bits.
+ * d2max_*: the published max |d2| slots; m1: the ReLU' mask words; needs
+ * net->conv_prep. */
 int acmi_debug_convt2(const acmi_net_t* net, int mode, const float* d2a, const float* d2b,
                       const uint32_t* m1, float* d1, int B, float* gram_part,
                       const uint32_t* d2max_a, const uint32_t* d2max_b, uint32_t* d1max,
                       acmi_stream_t stream);
+/* Diagnostic (tests, A/Bs): which form of conv2's input gradient acmi_backward and
+ * acmi_kfac_output_stats launch in this process: -1 = chosen by batch size (the
+ * default), 0 = always the staging form, 1 = always the resident form.  Returns
+ * the previous setting.  The forms are bit-identical; only speed differs. */
+int acmi_debug_convt2_form(int form);
 
 /* C[M][N] = A[M][K] @ B[K][N], row-major fp32, f32-input MFMA */
 int acmi_gemm_f32(const float* A, const float* B, float* C, int M, int N,

@@ -92,9 +92,11 @@ def stats_chain(M, reps=10):
 
 
 def c2mix(M, reps=20):
-    """conv2 dX of both K-FAC chains: the two launches of today (mode 0) against
-    the stacked launch (mode 1, acmi_debug_convt2), same lease, HIP events; and
-    the outputs (masked d1, max |d1|, Gram partials) compared bit for bit"""
+    """conv2 dX of both K-FAC chains: the two launches on the staging kernel (mode 0)
+    against the stacked launch (mode 1) and the two launches on the resident kernel
+    (mode 2, acmi_debug_convt2), same lease, HIP events, the outputs (masked d1,
+    max |d1|, Gram partials) compared bit for bit; then each launch alone at its
+    site in the update, per form (acmi_debug_convt2_form)"""
     from actorcritic._engine import NetEngine
     K_AMAX = 64 * 64  # kAmaxWords
     eng = NetEngine(4, 32)
@@ -119,7 +121,9 @@ def c2mix(M, reps=20):
     d2max_b = sd.ws[2 * K_AMAX:3 * K_AMAX]
     nb = 768
     outs = {}
-    for mode in (0, 1):
+    names = {0: 'two launches, staging', 1: 'stacked', 2: 'two launches, resident'}
+    has_resident = hasattr(_lib.load(), 'acmi_debug_convt2_form')  # (an older build under ACMI_LIB)
+    for mode in (0, 1, 2) if has_resident else (0, 1):
         d1 = torch.zeros_like(st.d1)
         gp = torch.zeros(nb * 33 * 32, device='cuda')
         d1max = torch.zeros(K_AMAX, dtype=torch.int32, device='cuda')
@@ -130,10 +134,26 @@ def c2mix(M, reps=20):
         torch.cuda.synchronize()
         outs[mode] = (d1.clone(), gp.clone(), d1max.max().item())
         ms = timeit(run, reps=reps, warm=3)
-        print('conv2 dX both chains, mode {} ({}): {:.1f} us'.format(mode, 'two launches' if mode == 0 else 'stacked',
-                                                                     1e3 * ms))
-    print('bit-identical: d1', torch.equal(outs[0][0], outs[1][0]), 'gram', torch.equal(outs[0][1], outs[1][1]),
-          'max|d1|', outs[0][2] == outs[1][2])
+        print('conv2 dX both chains, mode {} ({}): {:.1f} us'.format(mode, names[mode], 1e3 * ms))
+    for mode in sorted(outs)[1:]:
+        print('mode {} bit-identical to mode 0: d1'.format(mode), torch.equal(outs[0][0], outs[mode][0]), 'gram',
+              torch.equal(outs[0][1], outs[mode][1]), 'max|d1|', outs[0][2] == outs[mode][2])
+    # each launch alone at its site in the update (ACMI_PROF_CONV2_DX), per form
+    for form in (0, 1) if has_resident else (None,):
+        if form is not None:
+            _lib.load().acmi_debug_convt2_form(form)
+        for name, fn in (('loss chain (store)', lambda: eng.backward(f, st, True)),
+                         ('sampled chain (Gram)', lambda: eng.output_stats(f, st, 7, 3, side=sd))):
+            _lib.call('acmi_prof_enable', 5, 64)
+            timeit(fn, reps=reps, warm=2)
+            tot, cnt = ctypes.c_double(), ctypes.c_int()
+            _lib.call('acmi_prof_collect', ctypes.byref(tot), ctypes.byref(cnt))
+            _lib.call('acmi_prof_enable', 0, 0)
+            print('conv2 dX {} launch, {}: {:.1f} us over {}'.format(
+                name, {None: 'staging', 0: 'staging', 1: 'resident'}[form], 1e3 * tot.value / max(1, cnt.value),
+                cnt.value))
+    if has_resident:
+        _lib.load().acmi_debug_convt2_form(-1)
 
 
 def inverse(A=4, C3=32, reps=10):
