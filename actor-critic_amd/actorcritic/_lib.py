@@ -100,6 +100,8 @@ _SIGS = {
     'acmi_ppo_loss_ws_floats': (c_i64, [c_int]),
     'acmi_ppo_loss': (c_int, [c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_float, c_float,
                               c_float, c_float, c_float, c_vp, c_int, c_vp, c_vp, c_vp, c_vp]),
+    'acmi_gather_rows': (c_int, [c_vp, c_i64, c_i64, c_vp, c_i64, c_vp, c_i64, c_int, ctypes.POINTER(c_vp),
+                                 ctypes.POINTER(c_vp), c_vp, c_vp]),
     'acmi_backward_ws_floats': (c_i64, [c_int, c_int, c_int]),
     'acmi_backward': (c_int, [ctypes.POINTER(Net), c_vp, c_i64, c_int, ctypes.POINTER(Acts),
                               ctypes.POINTER(Bwd), c_vp, c_vp, c_vp, c_i64, c_vp]),

@@ -6,7 +6,8 @@ op; checkpoints and summaries are handled the same way.
 Defaults are the common Atari PPO setting (Schulman et al. 2017, table 5, at 32 envs):
 conv3 64, 32 envs x 128 steps, 4 epochs x 4 minibatches, clip 0.1, GAE(0.95) with
 batch-normalised advantages, Adam (epsilon 1e-5) at 2.5e-4 decayed linearly to 0, global
-gradient-norm clip 0.5.  Minibatches are env slices (objectives.PPOOptimizeOp).
+gradient-norm clip 0.5.  Minibatches are env slices by default; ``minibatch='rows'`` shuffles
+all env-steps of the batch per epoch (objectives.PPOOptimizeOp).
 """
 
 import os
@@ -25,10 +26,15 @@ from actorcritic.session import Session, get_or_create_global_step, no_op
 
 
 def train_ppo(env_id, num_envs, num_steps, checkpoint_path, model_name, summary_path=None, max_updates=None, seed=0,
-              log_every=10, num_epochs=4, num_minibatches=4, clip_range=0.1, value_clip_range=None):
+              log_every=10, num_epochs=4, num_minibatches=4, clip_range=0.1, value_clip_range=None,
+              minibatch='envs'):
     """Trains an Atari model (conv3 64) with PPO.
 
     ``num_envs`` is per GPU; with WORLD_SIZE > 1 (torchrun) every rank steps its own shard.
+    ``minibatch``: 'envs' (contiguous env slices of the batch; ``num_minibatches`` must divide
+    ``num_envs``) or 'rows' (the usual PPO minibatches: per epoch, a permutation of all
+    ``num_envs * num_steps`` rows cut into ``num_minibatches`` parts, which must divide that
+    product; costs a second copy of the batch's observations on the device).
     """
     parallel.init_from_env()
     multi_env = MultiEnv(create_environments(env_id, num_envs, seed=seed))
@@ -47,7 +53,7 @@ def train_ppo(env_id, num_envs, num_steps, checkpoint_path, model_name, summary_
     optimizer = create_optimizer(learning_rate)
     optimize_op = objective.optimize_shared(optimizer, baseline_loss_weight=0.5, num_epochs=num_epochs,
                                             num_minibatches=num_minibatches, shuffle_seed=seed,
-                                            global_step=global_step)
+                                            global_step=global_step, minibatch=minibatch)
 
     summary_writer = checkpoint.ScalarLog(summary_path) if (summary_path and parallel.rank() == 0) else None
     summary_op = no_op()

@@ -19,7 +19,8 @@ batch's mean and std).
 :class:`PPOObjective` (also beyond the reference) shares those targets and
 advantages and replaces the loss by PPO's clipped surrogate (acmi_ppo_loss); its
 ``optimize_shared`` op takes several epochs of minibatch gradient steps per
-``session.run`` (:class:`PPOOptimizeOp`).
+``session.run`` (:class:`PPOOptimizeOp`), over env slices of the batch or -- through a
+device row gather (acmi_gather_rows) -- over per-row shuffled minibatches.
 """
 
 from abc import ABCMeta, abstractmethod
@@ -260,6 +261,15 @@ def ppo_minibatch_order(shuffle_seed, step, num_epochs, num_minibatches):
     return [[int(j) for j in rng.permutation(int(num_minibatches))] for _ in range(int(num_epochs))]
 
 
+def ppo_row_order(shuffle_seed, step, num_epochs, M):
+    """The row order of every epoch of one PPO update with ``minibatch='rows'``: int32
+    permutations of range(M), one per epoch, from the host generator
+    :func:`ppo_minibatch_order` uses (seeded with (shuffle_seed, global step): no rank in
+    it, so every data-parallel rank draws the same orders)."""
+    rng = np.random.default_rng([int(shuffle_seed), int(step)])
+    return [rng.permutation(int(M)).astype(np.int32) for _ in range(int(num_epochs))]
+
+
 class _PPORun(object):
     """What one session.run shares between the PPO nodes."""
 
@@ -267,6 +277,10 @@ class _PPORun(object):
         self.st, self.fwd, self.actions, self.bufs = st, fwd, actions, bufs
         self.stepped = False  # the optimize op ran: the scalars are its last step's
         self.step_st = None
+
+    def vectors(self):
+        """The batch's per-row vectors in acmi_ppo_loss's order."""
+        return self.actions, self.bufs.old_logp, self.bufs.old_values, self.st.targets, self.st.adv
 
 
 class _PPOBuffers(object):
@@ -282,6 +296,30 @@ class _PPOBuffers(object):
             self.ws[M] = torch.zeros(int(eng.lib.acmi_ppo_loss_ws_floats(M)), dtype=torch.float32,
                                      device=eng.device)
         return self.ws[M]
+
+
+class _PPORowBuffers(object):
+    """The shuffled copy of an M-row batch that ``minibatch='rows'`` fills once per epoch
+    (acmi_gather_rows): observations (M x 28224 bytes) and the five per-row vectors in
+    :meth:`_PPORun.vectors`' order."""
+
+    def __init__(self, eng, M):
+        from actorcritic._engine import OBS_SHAPE
+        dev = eng.device
+        f = lambda: torch.zeros(M, dtype=torch.float32, device=dev)
+        self.obs = torch.zeros((M,) + tuple(OBS_SHAPE), dtype=torch.uint8, device=dev)
+        self.vecs = (torch.zeros(M, dtype=torch.int32, device=dev), f(), f(), f(), f())
+        self.dst = (_lib.c_vp * len(self.vecs))(*[v.data_ptr() for v in self.vecs])
+
+    def gather(self, eng, run, index):
+        """Row r of the copy <- row index[r] of the run's batch (one launch)."""
+        from actorcritic._engine import OBS_BYTES
+        M = self.obs.shape[0]
+        src = run.vectors()
+        assert all(a.dtype == b.dtype and a.numel() == M for a, b in zip(src, self.vecs))
+        src_ptrs = (_lib.c_vp * len(src))(*[_lib.ptr(v).value for v in src])
+        _lib.call('acmi_gather_rows', _lib.ptr(run.fwd.obs), OBS_BYTES, M, _lib.ptr(index), M, _lib.ptr(self.obs),
+                  OBS_BYTES, len(src), src_ptrs, self.dst, None, eng.stream())
 
 
 class _PPOBatch(Node):
@@ -325,7 +363,7 @@ class _PPOLoss(Node):
         run = ctx.eval(obj._batch_node)
         if not run.stepped:
             fwd, st, b = run.fwd, run.st, run.bufs
-            obj._launch_loss(fwd, 0, fwd.M, run, st.dhead, b.eval_out[:4], b.eval_out[4:])
+            obj._launch_loss(fwd, run.vectors(), 0, fwd.M, b, st.dhead, b.eval_out[:4], b.eval_out[4:])
         return run
 
     def scalars(self, ctx):
@@ -357,6 +395,10 @@ class PPOObjective(ActorCriticObjective):
     optionally batch-normalised) formed once per batch from the policy that collected
     it.  ``optimize_shared`` returns an op that takes ``num_epochs`` x
     ``num_minibatches`` gradient steps per ``session.run``.
+
+    ``normalize_advantages``: True (over the batch, once), False, or 'minibatch'
+    (baselines' / CleanRL's default: every gradient step normalises the advantages of
+    its own rows, all ranks' together; with ``optimize_shared(minibatch='rows')`` only).
     """
 
     def __init__(self, model, discount_factor=0.99, entropy_regularization_strength=0.01, clip_range=0.1,
@@ -368,10 +410,15 @@ class PPOObjective(ActorCriticObjective):
             raise ValueError('value_clip_range must be positive or None, got {}'.format(value_clip_range))
         if gae_lambda is not None and not 0.0 <= float(gae_lambda) <= 1.0:
             raise ValueError('gae_lambda must be in [0, 1] or None, got {}'.format(gae_lambda))
+        if isinstance(normalize_advantages, str) and normalize_advantages != 'minibatch':
+            raise ValueError("normalize_advantages must be True, False or 'minibatch', got {!r}"
+                             .format(normalize_advantages))
         self._model = model
         self._gamma = float(discount_factor)
         self._gae_lambda = None if gae_lambda is None else float(gae_lambda)
-        self._normalize = bool(normalize_advantages)
+        # 'minibatch': every gradient step normalises its own rows (PPOOptimizeOp), the batch is left alone
+        self._normalize_minibatch = normalize_advantages == 'minibatch'
+        self._normalize = not self._normalize_minibatch and bool(normalize_advantages)
         self._adv_eps = float(advantage_epsilon)
         self._beta = float(entropy_regularization_strength)
         self._clip = float(clip_range)
@@ -380,6 +427,7 @@ class PPOObjective(ActorCriticObjective):
         self._name = name or 'PPOObjective'
         self._table_cache = {}
         self._buffers = {}
+        self._row_buffers = {}
         self._targets_node = _Targets(self)
         self._batch_node = _PPOBatch(self)
         self._loss_node = _PPOLoss(self)
@@ -388,24 +436,30 @@ class PPOObjective(ActorCriticObjective):
 
     _tables = A2CObjective._tables
 
-    def _launch_loss(self, fwd, row0, rows, run, dhead, loss_out, clip_frac_out):
-        """acmi_ppo_loss of ``fwd`` (a forward of the batch rows row0 .. row0+rows-1)."""
+    def _launch_loss(self, fwd, vectors, row0, rows, bufs, dhead, loss_out, clip_frac_out):
+        """acmi_ppo_loss of ``fwd``, a forward of the rows row0 .. row0+rows-1 of the batch
+        whose (actions, old_logp, old_values, targets, adv) ``vectors`` are: the run's
+        own (:meth:`_PPORun.vectors`) or their shuffled copy (:class:`_PPORowBuffers`)."""
         eng = self._model.engine
-        b, sl = run.bufs, slice(row0, row0 + rows)
+        sl = slice(row0, row0 + rows)
+        actions, old_logp, old_values, targets, adv = (v[sl] for v in vectors)
         _lib.call('acmi_ppo_loss', _lib.ptr(fwd.flat_logits), eng.A, _lib.ptr(fwd.flat_value),
-                  _lib.ptr(run.actions[sl]), _lib.ptr(b.old_logp[sl]), _lib.ptr(b.old_values[sl]),
-                  _lib.ptr(run.st.targets[sl]), _lib.ptr(run.st.adv[sl]), rows, eng.A, self._clip, self._vclip,
+                  _lib.ptr(actions), _lib.ptr(old_logp), _lib.ptr(old_values),
+                  _lib.ptr(targets), _lib.ptr(adv), rows, eng.A, self._clip, self._vclip,
                   self._beta, float(self._vcoef), 1.0 / eng.world_size, _lib.ptr(dhead), eng.ldh,
-                  _lib.ptr(b.loss_ws(eng, rows)), _lib.ptr(loss_out), _lib.ptr(clip_frac_out), eng.stream())
+                  _lib.ptr(bufs.loss_ws(eng, rows)), _lib.ptr(loss_out), _lib.ptr(clip_frac_out), eng.stream())
 
     def optimize_shared(self, optimizer, baseline_loss_weight=0.5, num_epochs=4, num_minibatches=4, shuffle_seed=0,
-                        step_callback=None, global_step=None, **kwargs):
+                        step_callback=None, global_step=None, minibatch='envs', **kwargs):
         """The PPO update op: per ``session.run``, ``num_epochs`` passes over the batch
         in ``num_minibatches`` gradient steps each (see :class:`PPOOptimizeOp`).
 
-        Minibatches are contiguous ENV slices of the env-major [N][T] batch (so
-        ``num_minibatches`` must divide N: ValueError at run time otherwise); the
-        order of the slices is permuted per epoch, the rows are not shuffled."""
+        ``minibatch='envs'`` (the default): minibatches are contiguous ENV slices of the
+        env-major [N][T] batch (so ``num_minibatches`` must divide N: ValueError at run
+        time otherwise); the order of the slices is permuted per epoch, the rows are not
+        shuffled.  ``minibatch='rows'``: every epoch shuffles all N*T rows (a device
+        gather into a second copy of the batch) and cuts the shuffled batch into
+        ``num_minibatches`` equal parts (``num_minibatches`` must divide N*T)."""
         from actorcritic.kfac_utils import KfacOptimizer
         if isinstance(optimizer, KfacOptimizer):
             raise NotImplementedError('PPOObjective takes first-order optimizers only: K-FAC statistics of the '
@@ -414,9 +468,14 @@ class PPOObjective(ActorCriticObjective):
             raise TypeError('unexpected arguments {}'.format(sorted(kwargs)))
         if int(num_epochs) < 1 or int(num_minibatches) < 1:
             raise ValueError('num_epochs and num_minibatches must be at least 1')
+        if minibatch not in ('envs', 'rows'):
+            raise ValueError("minibatch must be 'envs' or 'rows', got {!r}".format(minibatch))
+        if self._normalize_minibatch and minibatch != 'rows':
+            raise ValueError("normalize_advantages='minibatch' needs minibatch='rows': an env slice is the batch's "
+                             "own memory, which a per-step normalisation would overwrite")
         self._vcoef = float(baseline_loss_weight)
         return PPOOptimizeOp(self, optimizer, int(num_epochs), int(num_minibatches), int(shuffle_seed),
-                             step_callback, global_step)
+                             step_callback, global_step, minibatch)
 
     @property
     def model(self):
@@ -463,31 +522,74 @@ class PPOOptimizeOp(Node):
        all-reduce, the optimizer's kernel, ``step_callback(epoch, position)``;
     3. ``global_step`` + 1 (once per run, not per gradient step).
 
-    Env-wise minibatching: a slice is the N / num_minibatches consecutive envs'
-    rows, read in place through pointer offsets; rows are not shuffled individually
-    (that needs a gather ahead of the tower).  ``last_order`` holds the slice order
+    Env-wise minibatching (``minibatch='envs'``, the default): a slice is the
+    N / num_minibatches consecutive envs' rows, read in place through pointer offsets;
+    rows are not shuffled individually.  ``last_order`` holds the slice order
     of the last run, ``[epoch][position] -> slice``.  The very first step of a run
     with one minibatch re-uses the batch's forward.
+
+    ``minibatch='rows'``: per epoch one acmi_gather_rows launch writes the batch's rows
+    (observations, actions, old log-probabilities / values, targets, advantages), in
+    the epoch's permutation (:func:`ppo_row_order`), into a second copy of the batch
+    (:class:`_PPORowBuffers`; M x 28224 bytes of observations); gradient step k of the
+    epoch then runs exactly as above on rows [k M/nmb, (k+1) M/nmb) of that copy, which
+    are contiguous again.  With ``normalize_advantages='minibatch'`` each step first
+    normalises its slice of the copied advantages in place (the next epoch gathers them
+    afresh from the batch's).  ``last_rows`` holds the last run's permutations,
+    ``[epoch] -> int32 ndarray`` (``last_order`` stays None); every step re-forwards.
     """
     name = 'ppo_optimize'
 
-    def __init__(self, objective, optimizer, num_epochs, num_minibatches, shuffle_seed, step_callback, global_step):
+    def __init__(self, objective, optimizer, num_epochs, num_minibatches, shuffle_seed, step_callback, global_step,
+                 minibatch='envs'):
+        if minibatch not in ('envs', 'rows'):
+            raise ValueError("minibatch must be 'envs' or 'rows', got {!r}".format(minibatch))
         self.objective, self.optimizer = objective, optimizer
         self.num_epochs, self.num_minibatches, self.shuffle_seed = num_epochs, num_minibatches, shuffle_seed
         self.step_callback = step_callback
         self.global_step = global_step
+        self.minibatch = minibatch
         self.last_order = None
+        self.last_rows = None
         self._runs = 0
 
     def _eval(self, ctx):
-        from actorcritic.envs.atari.model import ForwardOut
-        obj, opt = self.objective, self.optimizer
+        obj = self.objective
         eng = obj._model.engine
         run = ctx.eval(obj._batch_node)
+        step = self.global_step.value if self.global_step is not None else self._runs
+        if self.minibatch == 'rows':
+            st = self._epochs_of_rows(ctx, run, step)
+        else:
+            st = self._epochs_of_env_slices(ctx, run, step)
+        if eng.collective:  # (the other four scalars travel with the gradients)
+            from actorcritic import parallel
+            parallel.allreduce_sum_(run.bufs.clip_frac, force=True)
+        run.stepped, run.step_st = True, st
+        self._runs += 1
+        if self.global_step is not None:
+            self.global_step.assign(self.global_step.value + 1)
+        return None
+
+    def _step(self, ctx, run, part, vectors, row0, rows, epoch, pos):
+        """One gradient step on ``part``, a forward of rows row0 .. row0+rows-1 of ``vectors``' batch."""
+        obj, eng = self.objective, self.objective._model.engine
+        st = eng.update_state(rows)
+        obj._launch_loss(part, vectors, row0, rows, run.bufs, st.dhead, st.loss, run.bufs.clip_frac)
+        eng.backward(part, st, with_stats=False)
+        eng.allreduce(st, with_stats=False)
+        self.optimizer._apply_dense(ctx, eng, st.grads, 0.0)
+        eng.bump_version()
+        if self.step_callback is not None:
+            self.step_callback(epoch, pos)
+        return st
+
+    def _epochs_of_env_slices(self, ctx, run, step):
+        from actorcritic.envs.atari.model import ForwardOut
+        eng = self.objective._model.engine
         fwd = run.fwd
         T = fwd.steps
         slices = ppo_minibatch_rows(fwd.batch, T, self.num_minibatches)
-        step = self.global_step.value if self.global_step is not None else self._runs
         order = ppo_minibatch_order(self.shuffle_seed, step, self.num_epochs, self.num_minibatches)
         st = None
         for epoch, perm in enumerate(order):
@@ -500,23 +602,42 @@ class PPOOptimizeOp(Node):
                     obs = fwd.obs[row0:row0 + rows]
                     eng.forward(obs.data_ptr(), rows, acts.struct, want_value=True)
                     part = ForwardOut(eng, acts, rows // T, T, obs)
-                st = eng.update_state(rows)
-                obj._launch_loss(part, row0, rows, run, st.dhead, st.loss, run.bufs.clip_frac)
-                eng.backward(part, st, with_stats=False)
-                eng.allreduce(st, with_stats=False)
-                opt._apply_dense(ctx, eng, st.grads, 0.0)
-                eng.bump_version()
-                if self.step_callback is not None:
-                    self.step_callback(epoch, pos)
-        if eng.collective:  # (the other four scalars travel with the gradients)
-            from actorcritic import parallel
-            parallel.allreduce_sum_(run.bufs.clip_frac, force=True)
-        run.stepped, run.step_st = True, st
+                st = self._step(ctx, run, part, run.vectors(), row0, rows, epoch, pos)
         self.last_order = order
-        self._runs += 1
-        if self.global_step is not None:
-            self.global_step.assign(self.global_step.value + 1)
-        return None
+        return st
+
+    def _epochs_of_rows(self, ctx, run, step):
+        from actorcritic.envs.atari.model import ForwardOut
+        obj = self.objective
+        eng = obj._model.engine
+        M, nmb = run.fwd.M, self.num_minibatches
+        if M % nmb != 0:
+            raise ValueError('num_minibatches ({}) must divide the number of rows ({})'.format(nmb, M))
+        rows = M // nmb
+        order = [np.ascontiguousarray(p, dtype=np.int32) for p in
+                 ppo_row_order(self.shuffle_seed, step, self.num_epochs, M)]
+        for p in order:  # (host-side: the kernel would zero-fill a bad row, not fail)
+            if p.shape != (M,) or (M and (p.min() < 0 or p.max() >= M)):
+                raise ValueError('ppo_row_order must return indices into range({}) for every epoch'.format(M))
+        # one upload for the run's epochs: a copy from pageable memory waits for the stream
+        index = torch.from_numpy(np.stack(order)).to(eng.device)
+        sh = obj._row_buffers.get(M)
+        if sh is None:
+            sh = obj._row_buffers[M] = _PPORowBuffers(eng, M)
+        st = None
+        for epoch in range(len(order)):
+            sh.gather(eng, run, index[epoch])
+            for k in range(nmb):
+                row0 = k * rows
+                if obj._normalize_minibatch:
+                    _normalize_advantages(eng, sh.vecs[4][row0:row0 + rows], rows, obj._adv_eps)
+                acts = eng.activations(rows, 'ppo')
+                obs = sh.obs[row0:row0 + rows]
+                eng.forward(obs.data_ptr(), rows, acts.struct, want_value=True)
+                part = ForwardOut(eng, acts, rows, 1, obs)  # (a shuffled slice is not [env][step]-shaped)
+                st = self._step(ctx, run, part, sh.vecs, row0, rows, epoch, k)
+        self.last_rows = order
+        return st
 
 
 class _TargetView(Node):

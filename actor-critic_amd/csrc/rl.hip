@@ -1,5 +1,5 @@
 // Rollout-side and loss-side kernels: categorical sampling, n-step targets,
-// A2C and PPO losses + head gradients, first-order optimizers, batched synthetic Atari
+// A2C and PPO losses + head gradients, row gather, first-order optimizers, batched synthetic Atari
 // stepper with the reference's frame-stack / auto-reset / episode-info
 // semantics.  Contracts and reference citations: include/acmi.h.
 #include <math.h>
@@ -349,6 +349,69 @@ __global__ void ppo_loss_final_kernel(const float* part, int nb, int M, float be
 }
 
 // ---------------------------------------------------------------------------
+// row gather (PPO's shuffled minibatches; beyond the reference): a pure copy.
+// One block per output row: its 256 threads move the image's 1764 16-byte
+// words (lane-contiguous: 1 KiB per wave instruction; all of a thread's loads
+// are issued before its first store), thread 0 the row's <= 8 four-byte vector
+// elements.  An index outside [0, src_rows) zero-fills the row and counts it.
+// Without an image (obs == nullptr): one thread per row.
+// ---------------------------------------------------------------------------
+constexpr int GATHER_MAX_VECS = 8;
+constexpr int GATHER_BLOCK = 256;
+constexpr int GATHER_WORDS_PER_THREAD = (FRAME_WORDS + GATHER_BLOCK - 1) / GATHER_BLOCK;  // 7
+
+struct GatherVecs {
+  const uint32_t* src[GATHER_MAX_VECS];
+  uint32_t* dst[GATHER_MAX_VECS];
+};
+
+__device__ __forceinline__ void gather_row_vectors(const GatherVecs& v, int nvec, long long r, long long i,
+                                                   bool ok) {
+#pragma unroll
+  for (int k = 0; k < GATHER_MAX_VECS; ++k)
+    if (k < nvec) v.dst[k][r] = ok ? v.src[k][i] : 0u;
+}
+
+__global__ __launch_bounds__(GATHER_BLOCK) void gather_rows_kernel(
+    const uint8_t* obs, long long img_stride, long long src_rows, const int32_t* index, long long rows,
+    uint8_t* obs_out, long long out_stride, int nvec, GatherVecs vecs, int32_t* bad) {
+  if (!obs) {
+    const long long r = (long long)blockIdx.x * GATHER_BLOCK + threadIdx.x;
+    if (r >= rows) return;
+    const long long i = index[r];
+    const bool ok = i >= 0 && i < src_rows;
+    gather_row_vectors(vecs, nvec, r, i, ok);
+    if (!ok && bad) atomicAdd(bad, 1);
+    return;
+  }
+  const long long r = blockIdx.x;  // (the grid is exactly `rows` blocks)
+  const long long i = index[r];
+  const bool ok = i >= 0 && i < src_rows;  // uniform over the block
+  uint4* out = reinterpret_cast<uint4*>(obs_out + r * out_stride);
+  uint4 w[GATHER_WORDS_PER_THREAD];
+  if (ok) {
+    const uint4* in = reinterpret_cast<const uint4*>(obs + i * img_stride);
+#pragma unroll
+    for (int u = 0; u < GATHER_WORDS_PER_THREAD; ++u) {
+      const int g = threadIdx.x + u * GATHER_BLOCK;
+      if (g < FRAME_WORDS) w[u] = in[g];
+    }
+  } else {
+#pragma unroll
+    for (int u = 0; u < GATHER_WORDS_PER_THREAD; ++u) w[u] = make_uint4(0u, 0u, 0u, 0u);
+  }
+#pragma unroll
+  for (int u = 0; u < GATHER_WORDS_PER_THREAD; ++u) {
+    const int g = threadIdx.x + u * GATHER_BLOCK;
+    if (g < FRAME_WORDS) out[g] = w[u];
+  }
+  if (threadIdx.x == 0) {
+    gather_row_vectors(vecs, nvec, r, i, ok);
+    if (!ok && bad) atomicAdd(bad, 1);
+  }
+}
+
+// ---------------------------------------------------------------------------
 // deterministic global sum of squares / dot product (two passes)
 // ---------------------------------------------------------------------------
 constexpr int RED_BLOCKS = 512;
@@ -604,6 +667,35 @@ int acmi_ppo_loss(const float* logits, int ld, const float* values, const int32_
   hipLaunchKernelGGL(ppo_loss_final_kernel, dim3(1), dim3(64), 0, s, ws, nb, M, beta, grad_scale,
                      loss_out, clip_frac_out);
   ACMI_LAUNCH_CHECK("acmi_ppo_loss");
+  return ACMI_OK;
+}
+
+int acmi_gather_rows(const uint8_t* obs, int64_t img_stride, int64_t src_rows, const int32_t* index,
+                     int64_t rows, uint8_t* obs_out, int64_t out_stride, int nvec,
+                     const void* const* vec_src, void* const* vec_dst, int32_t* bad_rows,
+                     acmi_stream_t stream) {
+  constexpr int64_t kRowBytes = (int64_t)FRAME_WORDS * 16;
+  ACMI_REQUIRE(index && rows >= 0 && rows <= INT32_MAX && src_rows >= 0 && nvec >= 0 &&
+                   nvec <= GATHER_MAX_VECS && (nvec == 0 || (vec_src && vec_dst)),
+               ACMI_ERR_ARG, "acmi_gather_rows: bad arguments");
+  GatherVecs vecs = {};
+  for (int k = 0; k < nvec; ++k) {
+    ACMI_REQUIRE(vec_src[k] && vec_dst[k] && (uintptr_t)vec_src[k] % 4 == 0 && (uintptr_t)vec_dst[k] % 4 == 0,
+                 ACMI_ERR_ARG, "acmi_gather_rows: vector %d null or misaligned", k);
+    vecs.src[k] = static_cast<const uint32_t*>(vec_src[k]);
+    vecs.dst[k] = static_cast<uint32_t*>(vec_dst[k]);
+  }
+  if (obs)
+    ACMI_REQUIRE(obs_out && img_stride >= kRowBytes && out_stride >= kRowBytes && img_stride % 16 == 0 &&
+                     out_stride % 16 == 0 && (uintptr_t)obs % 16 == 0 && (uintptr_t)obs_out % 16 == 0,
+                 ACMI_ERR_ARG, "acmi_gather_rows: obs, obs_out and the strides (>= %lld) must be 16-byte aligned",
+                 (long long)kRowBytes);
+  if (rows == 0 || (!obs && nvec == 0)) return ACMI_OK;
+  const unsigned grid = obs ? (unsigned)rows : (unsigned)cdiv(rows, GATHER_BLOCK);
+  hipLaunchKernelGGL(gather_rows_kernel, dim3(grid), dim3(GATHER_BLOCK), 0, (hipStream_t)stream, obs,
+                     (long long)img_stride, (long long)src_rows, index, (long long)rows, obs_out,
+                     (long long)out_stride, nvec, vecs, bad_rows);
+  ACMI_LAUNCH_CHECK("acmi_gather_rows");
   return ACMI_OK;
 }
 

@@ -327,6 +327,27 @@ int acmi_ppo_loss(const float* logits, int ld, const float* values,
                   acmi_stream_t stream);
 
 /* ------------------------------------------------------------------------
+ * Row gather (PPO's shuffled minibatches; beyond the reference).
+ * For r in [0, rows): i = index[r];
+ *   image:   obs_out + r*out_stride  <-  obs + i*img_stride   (28224 bytes)
+ *   vectors: vec_dst[k][r] <- vec_src[k][i]  for k < nvec  (4-byte elements, bit copies)
+ * index values outside [0, src_rows) never touch memory outside the buffers: that
+ * output row (image and vectors) is zero-filled and *bad_rows (nullable, device int,
+ * accumulated) counts it.  Duplicates in index are allowed.  obs_out must not overlap
+ * obs; vec_dst[k] must not overlap vec_src[k].  obs, obs_out, img_stride, out_stride
+ * 16-byte aligned, both strides >= 28224; obs == NULL gathers the vectors only (obs_out
+ * and the strides are then ignored).  0 <= nvec <= 8; vec_src / vec_dst are host arrays
+ * of nvec device pointers (passed to the kernel by value).  rows == 0 is ACMI_OK
+ * without a launch; every argument error is ACMI_ERR_ARG before anything is enqueued.
+ * One launch, no allocation, no sync.
+ * ---------------------------------------------------------------------- */
+int acmi_gather_rows(const uint8_t* obs, int64_t img_stride, int64_t src_rows,
+                     const int32_t* index, int64_t rows,
+                     uint8_t* obs_out, int64_t out_stride,
+                     int nvec, const void* const* vec_src, void* const* vec_dst,
+                     int32_t* bad_rows, acmi_stream_t stream);
+
+/* ------------------------------------------------------------------------
  * Backward through the tower (the rest of tf.gradients, objectives.py:78)
  * fused with the K-FAC input-factor statistics (kfac cov_update_thunks,
  * kfac_utils.py:39,44; registration envs/atari/model.py:219-246):
