@@ -632,7 +632,10 @@ __global__ void kcoeff_kernel(const float* part, int nb, float lr, float c, floa
 
 // y[i][j] = sum_k A[i][k] g[k][j] for the narrow (dout % 4 != 0) first
 // products of the K-FAC step: block (i, j), one wave over k (fixed order:
-// lane-strided partial sums, then the butterfly)
+// lane-strided partial sums, then the butterfly).  The block of the last column
+// also zeroes the row's padding y[i][dout .. ldy): the second product reads t1
+// along k as float4 runs up to ldy (against zero rows of Ginv), so whatever the
+// workspace held there must not reach it (NaN * 0).
 __global__ __launch_bounds__(64) void kfac_narrow_kernel(const float* a, int lda, const float* g, int dout, int n,
                                                        float* y, int ldy) {
   const int i = blockIdx.x, j = blockIdx.y;
@@ -641,6 +644,8 @@ __global__ __launch_bounds__(64) void kfac_narrow_kernel(const float* a, int lda
   for (int k = threadIdx.x; k < n; k += 64) s += ar[k] * g[(long long)k * dout + j];
   s = wave_sum(s);
   if (threadIdx.x == 0) y[(long long)i * ldy + j] = s;
+  if (j == dout - 1 && threadIdx.x > 0 && dout + (int)threadIdx.x - 1 < ldy)
+    y[(long long)i * ldy + dout + threadIdx.x - 1] = 0.f;
 }
 
 __global__ void kapply_kernel(float* p, float* v, const float* d, long long n, float lr,

@@ -485,7 +485,8 @@ int acmi_kfac_eigvals(int num_actions, int conv3_filters, const float* factors,
  *   coeff = min(1, sqrt(norm_constraint / (lr^2 * sum_l <g_l, Delta_l>)));
  *   v = momentum*v + coeff*Delta;   params -= lr*v.
  * coeff is computed on the device (no host round trip); *coeff_out gets it.
- * ws: >= acmi_kfac_step_ws_floats() floats.
+ * ws: >= acmi_kfac_step_ws_floats() floats; scratch, its contents on entry do
+ * not matter.  precon (nparams floats) is an output.
  * ---------------------------------------------------------------------- */
 int64_t acmi_kfac_step_ws_floats(int num_actions, int conv3_filters);
 int acmi_kfac_step(int num_actions, int conv3_filters, float* params,
