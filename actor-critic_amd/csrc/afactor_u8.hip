@@ -211,7 +211,7 @@ __global__ __launch_bounds__(256) void conv1_afactor_i8_kernel(const uint8_t* ob
 // row), d1 rows staged beside them, so the u8 gather is shared by the A factor
 // and the weight gradient [P;1]^T d1.  Same A partial layout, so
 // conv1_afactor_finalize is shared; weight-gradient partials [chunk][257][32]
-// (row 256: the bias gradient) reduced by finalize_wgrad_kernel.  Roles (an
+// (row 256: the bias gradient) reduced by finalize_wgrad_body.  Roles (an
 // earlier form dealt the 36 A-factor tiles and the 8 weight-gradient tiles to
 // all 8 waves, so every wave read the whole split d1 operand -- about 230 KB of
 // LDS reads per stage, the column sums 8-way bank conflicted):

@@ -22,7 +22,7 @@
 //     GRAM: the masked tile goes through LDS ([ci][super-pixel], stride 36:
 //     conflict-free) and its Gram D D^T accumulates on bf16x3 MFMAs (d1 has no
 //     bound yet) across the wave's tiles; blocks write part[block][33][32] for
-//     finalize_cov_kernel (the layout gcov_layer's partials use).
+//     finalize_cov_wave_body (the layout gcov_layer's partials use).
 // k runs in gemm3's order (tap-major, channel-minor); d1 is f32-accurate.
 // (Measured on bf16x3, six MFMAs per product: 392 / 411 us per launch at
 // M = 10240.)
@@ -709,7 +709,7 @@ inline int convt2_store_blocks(int B) {
   const int ntiles = (B * CT2::L + CT2::TILE - 1) / CT2::TILE;
   return ACMI_CT2_STORE_BLOCKS > 0 ? std::max(1, std::min(ntiles, ACMI_CT2_STORE_BLOCKS)) : ntiles;
 }
-// blocks of the Gram variant (per-block partials, finalize_cov_kernel sums them)
+// blocks of the Gram variant (per-block partials, finalize_cov_wave_body sums them)
 inline int convt2_gram_blocks(int B) {
   const int ntiles = (B * CT2::L + CT2::TILE - 1) / CT2::TILE;
   return std::max(1, std::min(ntiles, 768));

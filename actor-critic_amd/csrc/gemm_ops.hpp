@@ -87,7 +87,7 @@ __device__ __forceinline__ StF4 stage_tail(const float* p, bool ok, int n) {
 // u8 pixels enter the MFMAs as their integer values 0..255 (exact in f32,
 // v_cvt_f32_ubyte0..3); the 1/255 of the reference's normalisation is applied
 // once per output by the consumer (EpiAct::scale for conv1, the conv1 weight
-// gradient's wscale in finalize_wgrad_kernel).
+// gradient's wscale in finalize_wgrad_body).
 __device__ __forceinline__ float4 finish(const StU8& s) {
   const uint32_t u = s.u;
   return make_float4((float)(u & 255u), (float)((u >> 8) & 255u), (float)((u >> 16) & 255u),

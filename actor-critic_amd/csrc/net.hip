@@ -754,664 +754,11 @@ static int forward_impl(const Layout& L, const float* P, const uint8_t* obs,
   return ACMI_OK;
 }
 
-// ---------------------------------------------------------------------------
-// split-K weight-gradient / factor reduction
-// ---------------------------------------------------------------------------
-// part: [nchunk][I+1][J] with J = kp + cout_pad + (kp ? 1 : 0).
-// grad (layer [W;b], (K+1) x cout, optionally split into two column groups
-// for the fused heads) and astat ((K+1)^2, symmetric, / rows).
-struct WgradDesc {
-  const float* part;
-  int nchunk;
-  int I;  // = K
-  int J;
-  int kp;       // 0 or K
-  int cout;
-  float* gradA;  // columns [0, nsplit)
-  int nsplit;
-  float* gradB;  // columns [nsplit, cout)
-  float* astat;  // nullable
-  int rows;
-  float wscale;  // applied to the weight rows (a < K) of the gradient
-};
+}  // namespace acmi
 
-// One block = 32 consecutive outputs x 8 chunk groups: group g sums chunks
-// g, g+8, ... in order (4 loads in flight), then the 8 group sums are added in
-// group order -- a fixed order (deterministic) with 8x the loads in flight of one
-// thread per output.  Outputs: the gradient rows (K+1) x cout, then the upper
-// triangle of the A factor (written to both halves).
-constexpr int kFinGroups = 8;
-__device__ __forceinline__ float chunk_sum_group(const float* p, int n, long long cs, int g) {
-  float s = 0.f;
-  for (int c0 = g; c0 < n; c0 += 4 * kFinGroups) {
-    float v[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int c = c0 + u * kFinGroups;
-      v[u] = p[(long long)(c < n ? c : g) * cs];
-    }
-#pragma unroll
-    for (int u = 0; u < 4; ++u) s += (c0 + u * kFinGroups < n) ? v[u] : 0.f;
-  }
-  return s;
-}
+#include "splitk.hpp"  // the split-K reduction: finalizes, plans, wgrad_layer / gcov_layer, workspace sizes
 
-__device__ __forceinline__ void finalize_wgrad_body(const WgradDesc& d, int bx, float (*red)[32]) {
-  const int K = d.I;
-  const long long ngrad = (long long)(K + 1) * d.cout;
-  const long long nstat = d.astat ? (long long)(K + 1) * (K + 1) : 0;
-  const int el = threadIdx.x & 31, g = threadIdx.x >> 5;
-  const long long idx = (long long)bx * 32 + el;
-  const long long cs = (long long)(d.I + 1) * d.J;  // chunk stride
-  // the partial this output sums (nullptr: nothing to sum)
-  const float* p = nullptr;
-  int a = 0, b = 0, n = 0;
-  if (idx < ngrad) {
-    a = (int)(idx / d.cout);
-    n = (int)(idx - (long long)a * d.cout);
-    const int row = a < K ? a : d.I;
-    p = d.part + (long long)row * d.J + d.kp + n;
-  } else if (idx < ngrad + nstat) {
-    const long long e = idx - ngrad;
-    a = (int)(e / (K + 1));
-    b = (int)(e - (long long)a * (K + 1));
-    // column K (the homogeneous coordinate) = sum of P = column-sum row
-    if (a <= b && a != K) p = b < K ? d.part + (long long)a * d.J + b : d.part + (long long)d.I * d.J + a;
-  }
-  red[g][el] = p ? chunk_sum_group(p, d.nchunk, cs, g) : 0.f;
-  __syncthreads();
-  if (g != 0 || idx >= ngrad + nstat) return;
-  float s = 0.f;
-#pragma unroll
-  for (int q = 0; q < kFinGroups; ++q) s += red[q][el];
-  if (idx < ngrad) {
-    if (a < K) s *= d.wscale;
-    if (n < d.nsplit) d.gradA[(long long)a * d.nsplit + n] = s;
-    else d.gradB[(long long)a * (d.cout - d.nsplit) + (n - d.nsplit)] = s;
-  } else {
-    if (a > b) return;
-    if (a == K) s = (float)d.rows;
-    s *= 1.0f / (float)d.rows;
-    d.astat[(long long)a * (K + 1) + b] = s;
-    d.astat[(long long)b * (K + 1) + a] = s;
-  }
-}
-
-// Gradient outputs (d.astat == nullptr) of a partial with few chunks (<= 8): one
-// thread per output instead of 32 outputs x 8 chunk groups per block (7 of the 8
-// groups idle at one chunk: the fc4 gradient's 803 K outputs were 25 K blocks).
-// The same sums in the same order: group g holds chunk g alone (0 + p[g]), the
-// groups added in order from 0.
-__device__ __forceinline__ void finalize_grad_thread_body(const WgradDesc& d, int bx) {
-  const int K = d.I;
-  const long long idx = (long long)bx * 256 + threadIdx.x;
-  if (idx >= (long long)(K + 1) * d.cout) return;
-  const int a = (int)(idx / d.cout), n = (int)(idx - (long long)a * d.cout);
-  const float* p = d.part + (long long)(a < K ? a : d.I) * d.J + d.kp + n;
-  const long long cs = (long long)(d.I + 1) * d.J;
-  float v[kFinGroups];
-#pragma unroll
-  for (int g = 0; g < kFinGroups; ++g) v[g] = p[(long long)(g < d.nchunk ? g : 0) * cs];
-  float s = 0.f;
-#pragma unroll
-  for (int g = 0; g < kFinGroups; ++g) s += g < d.nchunk ? 0.f + v[g] : 0.f;
-  if (a < K) s *= d.wscale;
-  if (n < d.nsplit) d.gradA[(long long)a * d.nsplit + n] = s;
-  else d.gradB[(long long)a * (d.cout - d.nsplit) + (n - d.nsplit)] = s;
-}
-__device__ __forceinline__ bool fin_thread_ok(const WgradDesc& d) { return !d.astat && d.nchunk <= kFinGroups; }
-inline int fin_blocks(const WgradDesc& d) {
-  const long long total = (long long)(d.I + 1) * d.cout + (d.astat ? (long long)(d.I + 1) * (d.I + 1) : 0);
-  return (int)(!d.astat && d.nchunk <= kFinGroups ? cdiv(total, 256) : cdiv(total, 32));
-}
-
-__global__ __launch_bounds__(256) void finalize_wgrad_kernel(WgradDesc d) {
-  __shared__ float red[kFinGroups][32];
-  if (fin_thread_ok(d)) finalize_grad_thread_body(d, blockIdx.x);
-  else finalize_wgrad_body(d, blockIdx.x, red);
-}
-
-// The A factor of a split-K wgrad partial ((K+1)^2, symmetric): one block per
-// 32x32 tile of the upper triangle; each element sums its chunks in exactly
-// finalize_wgrad_kernel's order (chunk group g = c mod 8 in chunk order, then
-// the groups in order), is stored at (a, b) and, through an LDS transpose, at
-// (b, a) -- both halves written by coalesced rows (the element-per-thread
-// mirror store of finalize_wgrad_kernel is a 4-byte scatter with stride K+1).
-__device__ __forceinline__ void finalize_afactor_body(const WgradDesc& d, int ntile, int bx, float (*tr)[33]) {
-  const int K = d.I, K1 = K + 1;
-  // upper-triangle tile (ta <= tb) of linear index bx
-  int t = bx, ta = 0;
-  while (t >= ntile - ta) t -= ntile - ta, ++ta;
-  const int tb = ta + t;
-  const long long cs = (long long)(d.I + 1) * d.J;
-  const int c = threadIdx.x & 31, r0 = threadIdx.x >> 5;
-  const float inv = 1.0f / (float)d.rows;
-#pragma unroll
-  for (int it = 0; it < 4; ++it) {
-    const int r = r0 + 8 * it;
-    const int a = 32 * ta + r, b = 32 * tb + c;
-    float v = 0.f;
-    if (a < K1 && b < K1 && a <= b) {
-      if (a == K) {
-        v = (float)d.rows * inv;  // rows * fl(1/rows), as finalize_wgrad_kernel (1 - 2^-24 for some rows)
-      } else {
-        const float* p = b < K ? d.part + (long long)a * d.J + b : d.part + (long long)d.I * d.J + a;
-        float s = 0.f;
-        for (int g = 0; g < kFinGroups; ++g) {
-          float sg = 0.f;
-          for (int ch = g; ch < d.nchunk; ch += kFinGroups) sg += p[(long long)ch * cs];
-          s += sg;
-        }
-        v = s * inv;
-      }
-      d.astat[(long long)a * K1 + b] = v;
-    }
-    tr[r][c] = v;
-  }
-  __syncthreads();
-#pragma unroll
-  for (int it = 0; it < 4; ++it) {  // (b, a) for a < b: row b of the output reads column b of the tile
-    const int r = r0 + 8 * it;     // row offset inside tile tb
-    const int b = 32 * tb + r, a = 32 * ta + c;
-    if (a < K1 && b < K1 && a < b) d.astat[(long long)b * K1 + a] = tr[c][r];
-  }
-}
-__global__ __launch_bounds__(256) void finalize_afactor_kernel(WgradDesc d, int ntile) {
-  __shared__ float tr[32][33];
-  finalize_afactor_body(d, ntile, blockIdx.x, tr);
-}
-
-// Several layers' weight-gradient / A-factor finalizes as one launch (each
-// layer's split-K partials in their own workspace range): task k owns blocks
-// [blk0, blk0 of k+1) and runs finalize_wgrad_kernel's (kind 0) or
-// finalize_afactor_kernel's (kind 1) body -- the same sums.
-struct WgradTask {
-  WgradDesc d;
-  int kind, ntile, blk0;
-};
-constexpr int kWgradTasks = 6;
-struct WgradSet {
-  int n = 0;
-  int blocks = 0;
-  WgradTask t[kWgradTasks];
-  void add(const WgradDesc& d, int kind, int ntile, int nblocks) {
-    t[n++] = WgradTask{d, kind, ntile, blocks};
-    blocks += nblocks;
-  }
-};
-__global__ __launch_bounds__(256) void finalize_wgrad_multi_kernel(WgradSet S) {
-  __shared__ float red[kFinGroups][32];
-  __shared__ float tr[32][33];
-  int k = 0;
-  while (k + 1 < S.n && (int)blockIdx.x >= S.t[k + 1].blk0) ++k;
-  const WgradTask& T = S.t[k];
-  const int b = blockIdx.x - T.blk0;
-  if (T.kind == 0) {
-    if (fin_thread_ok(T.d)) finalize_grad_thread_body(T.d, b);
-    else finalize_wgrad_body(T.d, b, red);
-  } else {
-    finalize_afactor_body(T.d, T.ntile, b, tr);
-  }
-}
-
-// G factor: part [nchunk][I+1][J] (I == J == n, no colsum row used); one
-// wave per output element sums the chunks in a fixed (lane-strided, then
-// butterfly) order, so the result is deterministic.
-// thread per upper-triangle element (few chunks): consecutive threads read
-// consecutive partials, the value is written to both halves
-__global__ void finalize_cov_thread_kernel(const float* part, int nchunk, int n, int sub,
-                                           float* out, int rows) {
-  const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= sub * sub) return;
-  const int a = idx / sub, b = idx - a * sub;
-  if (a > b) return;
-  const long long cs = (long long)(n + 1) * n;
-  const float v = chunk_sum(part + (long long)a * n + b, nchunk, cs) * (1.0f / (float)rows);
-  out[a * sub + b] = v;
-  out[b * sub + a] = v;
-}
-
-// wave per element (many chunks: the lanes split the chunks)
-__global__ void finalize_cov_kernel(const float* part, int nchunk, int n,
-                                    int sub, float* out, int rows) {
-  // out is sub x sub, taken from the top-left of the n x n product
-  const int idx = blockIdx.x * 4 + (threadIdx.x >> 6);
-  const int lane = threadIdx.x & 63;
-  if (idx >= sub * sub) return;
-  const int a = idx / sub, b = idx - a * sub;
-  const int lo = a < b ? a : b, hi = a < b ? b : a;
-  const long long cs = (long long)(n + 1) * n;
-  const float* p = part + (long long)lo * n + hi;
-  float s = 0.f;
-  for (int c = lane; c < nchunk; c += 64) s += p[c * cs];
-  s = wave_sum(s);
-  if (lane == 0) out[idx] = s * (1.0f / (float)rows);
-}
-
-// G of the value head: element (A, A) of the heads product
-__global__ void finalize_cov_elem_kernel(const float* part, int nchunk, int n,
-                                         int a, float* out, int rows) {
-  // one wave: lane-strided partial sums + a butterfly (fixed order)
-  const int lane = threadIdx.x & 63;
-  if (threadIdx.x >= 64 || blockIdx.x != 0) return;
-  const long long cs = (long long)(n + 1) * n;
-  const float* p = part + (long long)a * n + a;
-  float s = 0.f;
-  for (int c = lane; c < nchunk; c += 64) s += p[c * cs];
-  s = wave_sum(s);
-  if (lane == 0) out[0] = s * (1.0f / (float)rows);
-}
-
-// The sampled-loss chain's G-factor finalizes as ONE launch after all its Grams
-// (each Gram's partials in its own workspace range): task k owns blocks
-// [blk0, blk0 of k+1) and runs the body of finalize_cov_thread_kernel (kind 0),
-// finalize_cov_kernel (1) or finalize_cov_elem_kernel (2) -- the same sums.
-struct CovTask {
-  const float* part;
-  float* out;
-  int nchunk, n, sub, rows, kind, a, blk0;
-};
-constexpr int kCovTasks = 8;
-struct CovSet {
-  int n = 0;
-  int blocks = 0;
-  CovTask t[kCovTasks];
-  void add(const float* part, int nchunk, int n_, int sub, float* out, int rows, int kind, int a = 0) {
-    const int nt = cdiv(sub, 32);
-    const int nb = kind == 0 ? cdiv(sub * sub, 256) : kind == 1 ? cdiv(sub * sub, 4) : kind == 3 ? nt * (nt + 1) / 2 : 1;
-    t[n++] = CovTask{part, out, nchunk, n_, sub, rows, kind, a, blocks};
-    blocks += nb;
-  }
-};
-__global__ __launch_bounds__(256) void finalize_cov_multi_kernel(CovSet S) {
-  int k = 0;
-  while (k + 1 < S.n && (int)blockIdx.x >= S.t[k + 1].blk0) ++k;
-  const CovTask& T = S.t[k];
-  const int b = blockIdx.x - T.blk0;
-  const long long cs = (long long)(T.n + 1) * T.n;
-  if (T.kind == 3) {
-    // kind 0's sums on 32 x 32 upper-triangle tiles, both halves written by
-    // coalesced rows through an LDS transpose (kind 0's mirror store is a 4-byte
-    // scatter with stride sub: the 512-wide G factor's half)
-    __shared__ float tr[32][33];
-    const int ntile = (T.sub + 31) / 32;
-    int t = b, ta = 0;
-    while (t >= ntile - ta) t -= ntile - ta, ++ta;
-    const int tb = ta + t;
-    const int c = threadIdx.x & 31, r0 = threadIdx.x >> 5;
-#pragma unroll
-    for (int it = 0; it < 4; ++it) {
-      const int r = r0 + 8 * it;
-      const int a = 32 * ta + r, cc = 32 * tb + c;
-      float v = 0.f;
-      if (a < T.sub && cc < T.sub && a <= cc) {
-        v = chunk_sum(T.part + (long long)a * T.n + cc, T.nchunk, cs) * (1.0f / (float)T.rows);
-        T.out[a * T.sub + cc] = v;
-      }
-      tr[r][c] = v;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int it = 0; it < 4; ++it) {
-      const int r = r0 + 8 * it;
-      const int bb = 32 * tb + r, a = 32 * ta + c;
-      if (a < T.sub && bb < T.sub && a < bb) T.out[bb * T.sub + a] = tr[c][r];
-    }
-    return;
-  }
-  if (T.kind == 0) {
-    const int idx = b * 256 + threadIdx.x;
-    if (idx >= T.sub * T.sub) return;
-    const int a = idx / T.sub, c = idx - a * T.sub;
-    if (a > c) return;
-    const float v = chunk_sum(T.part + (long long)a * T.n + c, T.nchunk, cs) * (1.0f / (float)T.rows);
-    T.out[a * T.sub + c] = v;
-    T.out[c * T.sub + a] = v;
-  } else {
-    const int idx = T.kind == 1 ? b * 4 + (threadIdx.x >> 6) : 0;
-    const int lane = threadIdx.x & 63;
-    if (idx >= T.sub * T.sub || (T.kind == 2 && threadIdx.x >= 64)) return;
-    int lo, hi;
-    if (T.kind == 1) {
-      const int a = idx / T.sub, c = idx - a * T.sub;
-      lo = a < c ? a : c, hi = a < c ? c : a;
-    } else {
-      lo = hi = T.a;
-    }
-    const float* p = T.part + (long long)lo * T.n + hi;
-    float v = 0.f;
-    for (int c = lane; c < T.nchunk; c += 64) v += p[c * cs];
-    v = wave_sum(v);
-    if (lane == 0) T.out[idx] = v * (1.0f / (float)T.rows);
-  }
-}
-
-// G = D^T D for narrow D (n <= NP, NP in {32, 64}) straight from global memory:
-// each wave streams row pairs (lane l: row 2q + (l>>5), column l&31 [+32]) as
-// the A and B fragments of v_mfma_f32_32x32x2_f32 (the Gram tile is D^T D of
-// the same registers).  Two register sets of UNR k-steps: the next group's
-// loads are issued before this group's MFMAs.  The block's 4 waves are summed
-// into one LDS image in wave order (deterministic) and stored as
-// part[chunk][NP+1][NP] (finalize_cov_*).
-template <int NP>
-__global__ __launch_bounds__(256) void gram_small_kernel(const float* D, int ld, int n,
-                                                        long long rows, long long chunk,
-                                                        float* part) {
-  constexpr int T = NP / 32;           // column tiles
-  constexpr int NT = T * (T + 1) / 2;  // upper-triangle tile pairs
-  constexpr int UNR = 8;
-  __shared__ float red[NP * NP];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int h = lane >> 5, c = lane & 31;
-  const long long r0 = (long long)blockIdx.x * chunk;
-  const long long r1 = min(rows, r0 + chunk);
-  f32x16 acc[NT];
-#pragma unroll
-  for (int t = 0; t < NT; ++t)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
-  const float* zero = zero_run();
-  auto load = [&](long long base, float (&v)[UNR][T]) {
-#pragma unroll
-    for (int u = 0; u < UNR; ++u) {
-      const long long row = base + 8 * u + h;
-#pragma unroll
-      for (int t = 0; t < T; ++t) {
-        const int col = c + 32 * t;
-        const bool ok = row < r1 && col < n;
-        v[u][t] = *(ok ? D + row * ld + col : zero);
-      }
-    }
-  };
-  auto mma = [&](const float (&v)[UNR][T]) {
-#pragma unroll
-    for (int u = 0; u < UNR; ++u) {
-      int t = 0;
-#pragma unroll
-      for (int x = 0; x < T; ++x)
-#pragma unroll
-        for (int y = x; y < T; ++y, ++t)
-          acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(v[u][x], v[u][y], acc[t], 0, 0, 0);
-    }
-  };
-  float va[UNR][T], vb[UNR][T];
-  long long base = r0 + 2 * wave;
-  load(base, va);
-  for (; base < r1; base += 16 * UNR) {
-    load(base + 8 * UNR, vb);
-    mma(va);
-    if (base + 8 * UNR >= r1) break;
-    load(base + 16 * UNR, va);
-    mma(vb);
-  }
-  // acc[t][r]: tile (x, y), row 32x + (r&3) + 8(r>>2) + 4h, column 32y + c
-  for (int w = 0; w < 4; ++w) {
-    if (wave == w) {
-      int t = 0;
-#pragma unroll
-      for (int x = 0; x < T; ++x)
-#pragma unroll
-        for (int y = x; y < T; ++y, ++t)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) {
-            const int i = 32 * x + (r & 3) + 8 * (r >> 2) + 4 * h, j = 32 * y + c;
-            const float prev_ij = w ? red[i * NP + j] : 0.f;
-            red[i * NP + j] = prev_ij + acc[t][r];
-            if (x != y) {
-              const float prev_ji = w ? red[j * NP + i] : 0.f;
-              red[j * NP + i] = prev_ji + acc[t][r];
-            }
-          }
-    }
-    __syncthreads();
-  }
-  float* out = part + (long long)blockIdx.x * (NP + 1) * NP;
-  for (int e = threadIdx.x; e < NP * NP; e += 256) out[e] = red[e];
-}
-
-// split-K reductions fill whole rounds of resident blocks (plan_rounds):
-// MI355X has 256 CUs; blocks per CU follow from each config's LDS image
-constexpr int kCUs = 256;
-
-static bool band_on(bool with_stats) {
-  return with_stats && g_gemm_mode == ACMI_GEMM_X3 && g_conv_stats_mode == ACMI_CONV_STATS_BAND;
-}
-
-struct WgradPlan {
-  int I, J, kp, cout_pad, nc, ch;
-  bool slabs;  // symred_kernel (slab groups) instead of 128x128 live tiles
-  bool six;    // bf16x3 six-slab groups (symred6_kernel)
-  bool six_greedy = false;  // ... with the greedy plan for any K (fc4)
-  SymPlan sp;
-  SymPlan6 sp6;
-  long long floats;
-};
-
-static WgradPlan wgrad_plan(int K, int cout, bool with_stats, long long rows, bool u8 = false,
-                            int mode = g_gemm_mode) {
-  WgradPlan p;
-  p.cout_pad = roundup4(cout);
-  p.kp = with_stats ? K : 0;
-  p.I = K;
-  // no homogeneous column: the A factor's last column (sum of P) is the
-  // column-sum row's P part, by symmetry
-  p.J = p.kp + p.cout_pad;
-  p.slabs = with_stats && sym_plan(K, p.cout_pad, &p.sp);  // (f32 patch sources only)
-  p.six = p.slabs && mode == ACMI_GEMM_X3 && sym_plan6(K, p.cout_pad, &p.sp6);
-  // fc4 (K = 1568, no four-slab plan): greedy six-slab groups instead of 128x128 tiles
-  p.six_greedy = !p.slabs && !u8 && with_stats && mode == ACMI_GEMM_X3 && K % 4 == 0 &&
-                 sym_plan6_greedy(K, p.cout_pad, &p.sp6);
-  if (p.six_greedy) p.six = true;
-  if (u8)  // conv1 weight gradient: conv1_wgrad_u8/x3_kernel, one 256x32 block per chunk
-    conv1_wgrad_u8_plan(rows, &p.nc, &p.ch, mode);
-  else if (p.six_greedy)  // many groups: one round of blocks, few chunks (partials stay small)
-    plan_rounds(rows, p.sp6.ngroups, kCUs, &p.nc, &p.ch, 2048);
-  else if (p.six)  // one 512-thread block per CU (2 x 64 accumulators per wave)
-    plan_rounds(rows, p.sp6.ngroups, kCUs, &p.nc, &p.ch);
-  else if (p.slabs && mode == ACMI_GEMM_X3)
-    plan_rounds(rows, p.sp.ngroups, kCUs * std::min(8, 160 * 1024 / symred3_lds_bytes()), &p.nc,
-                &p.ch);
-  else if (p.slabs)
-    plan_rounds(rows, p.sp.ngroups, kCUs * std::min(8, 160 * 1024 / symred_lds_bytes<16>()), &p.nc,
-                &p.ch);
-  else if (with_stats)
-    plan_rounds(rows, live_tiles<128, 128>(p.I, p.J, K),
-                kCUs * gemm_blocks_per_cu<128, 128, 16, false, false>(), &p.nc, &p.ch);
-  else
-    plan_rounds(rows, live_tiles<128, 32>(p.I, p.J, 0),
-                kCUs * gemm_blocks_per_cu<128, 32, 32, false, false>(), &p.nc, &p.ch);
-  p.floats = (long long)p.nc * (p.I + 1) * p.J;
-  return p;
-}
-
-struct GcovPlan {
-  int np, nc, ch;
-  long long floats;
-};
-
-// narrow Gram: chunks of >= 512 rows, at most 2048 blocks (8 per CU)
-static void gram_plan(long long rows, int* nc, long long* chunk) {
-  long long n = std::min<long long>(2048, std::max<long long>(1, rows / 512));
-  long long ch = (rows + n - 1) / n;
-  ch = (ch + 63) / 64 * 64;
-  *chunk = ch;
-  *nc = (int)((rows + ch - 1) / ch);
-}
-
-static GcovPlan gcov_plan(int n, long long rows) {
-  GcovPlan p;
-  p.np = roundup4(n);
-  plan_rounds(rows, live_tiles<64, 64>(p.np, p.np, p.np),
-              kCUs * gemm_blocks_per_cu<64, 64, 32, false, false>(), &p.nc, &p.ch);
-  p.floats = (long long)p.nc * (p.np + 1) * p.np;
-  return p;
-}
-
-// the partial floats gcov_layer will need (its two paths' plans)
-static long long gcov_need(int n, long long rows) {
-  if (n <= 32) {
-    int nc;
-    long long ch;
-    gram_plan(rows, &nc, &ch);
-    return (long long)nc * 33 * 32;
-  }
-  return gcov_plan(n, rows).floats;
-}
-
-// Launch [P;1]^T [P | dY] (with_stats; the 1 row is the column-sum row) or
-// [P;1]^T [dY] over rows.
-template <class Src>
-static int wgrad_layer(const Src& src, int K, long long rows, const float* dy,
-                       int ldy, int cout, bool with_stats, float* part,
-                       long long part_cap, float* gradA, int nsplit,
-                       float* gradB, float* astat, hipStream_t s, int site = 0,
-                       float wscale = 1.f, const unsigned* pmax = nullptr, const unsigned* ymax = nullptr,
-                       WgradSet* defer = nullptr, long long* used = nullptr) {
-  constexpr bool kU8 = !std::is_same<typename Src::elem_t, float>::value;
-  const int mode = g_gemm_mode;
-  const WgradPlan pl = wgrad_plan(K, cout, with_stats, rows, kU8, mode);
-  const int I = pl.I, J = pl.J, kp = pl.kp, nc = pl.nc, ch = pl.ch;
-  RowsAsI<Src> opA{src};
-  CatRowsI<Src> opB{src, kp, dy, ldy, cout, pl.cout_pad, (int)rows};
-  if constexpr (!std::is_same<typename Src::elem_t, float>::value)
-    ACMI_REQUIRE(!with_stats, ACMI_ERR_ARG, "u8 patch sources take the integer A-factor path");
-  ACMI_REQUIRE(pl.floats <= part_cap, ACMI_ERR_WS, "wgrad workspace too small (%lld > %lld)",
-               pl.floats, part_cap);
-  EpiPartial epi{part, I, J};
-  prof_begin(site, s);
-  if constexpr (std::is_same<typename Src::elem_t, float>::value) {
-    if (pl.six)  // six-slab groups, bf16x3 split operands (f16x2 with published bounds)
-      launch_symred6(opB, epi, pl.sp6, I, J, (int)rows, nc, ch, s, pmax, ymax, kp);
-    else if (pl.slabs && mode == ACMI_GEMM_X3)  // slab groups, bf16x3 split operands
-      launch_symred3(opB, epi, pl.sp, I, J, (int)rows, nc, ch, s);
-    else if (pl.slabs)  // slab groups over the upper triangle of P^T P and the dY columns
-      launch_symred<16>(opB, epi, pl.sp, I, J, (int)rows, nc, ch, s);
-    else if (with_stats)  // 128x128 live tiles (fc4: K not a multiple of 64)
-      launch_mm<128, 128, 16, 2, 2, true, true, 16>(opA, opB, epi, I, J, (int)rows, nc, ch, s, K);
-    else
-      launch_mm<128, 32, 32, 1, 1, true, true, 32>(opA, opB, epi, I, J, (int)rows, nc, ch, s);
-  } else {  // u8 patches (conv1): weight gradient only, bytes in LDS
-    ACMI_REQUIRE(K == 256 && cout == 32 && ldy == 32, ACMI_ERR_ARG, "conv1 weight gradient shape");
-    launch_conv1_wgrad_u8(src, dy, (int)rows, nc, ch, epi, s);
-  }
-  prof_end(site, s);
-  // few chunks (fc4): the A factor on upper-triangle tiles mirrored through LDS;
-  // many (the heads' 80): one output per 8 threads, chunk groups in parallel
-  const bool tiles = astat && nc <= kFinGroups;
-  WgradDesc d{part, nc, I, J, kp, cout, gradA, nsplit, gradB, tiles ? nullptr : astat, (int)rows, wscale};
-  if (used) *used = pl.floats;
-  if (defer) {
-    defer->add(d, 0, 0, fin_blocks(d));
-    if (tiles) {
-      d.astat = astat;
-      const int nt = cdiv(K + 1, 32);
-      defer->add(d, 1, nt, nt * (nt + 1) / 2);
-    }
-    ACMI_LAUNCH_CHECK("wgrad_layer");
-    return ACMI_OK;
-  }
-  hipLaunchKernelGGL(finalize_wgrad_kernel, dim3(fin_blocks(d)), dim3(256), 0, s, d);
-  if (tiles) {
-    d.astat = astat;
-    const int nt = cdiv(K + 1, 32);
-    hipLaunchKernelGGL(finalize_afactor_kernel, dim3(nt * (nt + 1) / 2), dim3(256), 0, s, d, nt);
-  }
-  ACMI_LAUNCH_CHECK("wgrad_layer");
-  return ACMI_OK;
-}
-
-// G = g^T g / rows for g [rows][ld] (first n columns), via split-K; gmax: the
-// published max |g| (bit pattern) -- the wide Grams then run on f16x2 split
-// operands (three MFMAs per product instead of bf16x3's six)
-// defer: append the finalize to this set instead of launching it (the caller
-// launches the set once; *used: the partial floats this Gram wrote)
-static int gcov_layer(const float* g, int ld, int n, long long rows, int sub,
-                      float* part, long long part_cap, float* out,
-                      hipStream_t s, float* out_v = nullptr, int v_index = -1,
-                      const unsigned* gmax = nullptr, CovSet* defer = nullptr, long long* used = nullptr) {
-  int np, nc;
-  if (n <= 32) {  // narrow: streaming Gram kernel (f32 MFMA; 64 wide runs faster on the split-K
-                  // bf16x3 GEMM below: conv2's G factor 82 + 25 -> 59 + 16 us)
-    np = n <= 32 ? 32 : 64;
-    long long ch;
-    gram_plan(rows, &nc, &ch);
-    ACMI_REQUIRE((long long)nc * (np + 1) * np <= part_cap, ACMI_ERR_WS, "gcov workspace too small");
-    if (np == 32)
-      hipLaunchKernelGGL(gram_small_kernel<32>, dim3(nc), dim3(256), 0, s, g, ld, n, rows, ch, part);
-    else
-      hipLaunchKernelGGL(gram_small_kernel<64>, dim3(nc), dim3(256), 0, s, g, ld, n, rows, ch, part);
-  } else {
-    const GcovPlan pl = gcov_plan(n, rows);
-    np = pl.np;
-    nc = pl.nc;
-    DenseRows src{g, ld, (int)rows, np};
-    RowsAsI<DenseRows> op{src};
-    ACMI_REQUIRE(pl.floats <= part_cap, ACMI_ERR_WS, "gcov workspace too small");
-    EpiPartial epi{part, np, np};
-    if (gmax && g_gemm_mode == ACMI_GEMM_X3)
-      launch_gemm3_f16_splitk<64, 64, 16, 1, 1>(op, op, epi, np, np, (int)rows, nc, (int)pl.ch, gmax, gmax, s, np);
-    else
-      launch_mm<64, 64, 32, 1, 1, true, false, 16>(op, op, epi, np, np, (int)rows, nc, pl.ch, s, np);
-  }
-  if (used) *used = (long long)nc * (np + 1) * np;
-  if (defer) {
-    defer->add(part, nc, np, sub, out, (int)rows, nc <= 64 ? (sub >= 64 ? 3 : 0) : 1);
-    if (out_v) defer->add(part, nc, np, 1, out_v, (int)rows, 2, v_index);
-    ACMI_LAUNCH_CHECK("gcov_layer");
-    return ACMI_OK;
-  }
-  if (nc <= 64)
-    hipLaunchKernelGGL(finalize_cov_thread_kernel, dim3(cdiv((long long)sub * sub, 256)), dim3(256), 0,
-                       s, part, nc, np, sub, out, (int)rows);
-  else
-    hipLaunchKernelGGL(finalize_cov_kernel, dim3(cdiv((long long)sub * sub, 4)), dim3(256), 0,
-                       s, part, nc, np, sub, out, (int)rows);
-  if (out_v)
-    hipLaunchKernelGGL(finalize_cov_elem_kernel, dim3(1), dim3(64), 0, s, part, nc, np,
-                       v_index, out_v, (int)rows);
-  ACMI_LAUNCH_CHECK("gcov_layer");
-  return ACMI_OK;
-}
-
-// the split-K partial region's minimum: the largest partial over all layers (with
-// stats, both gemm modes, both Gram paths, the band reductions)
-static long long bwd_partial_floats(int B, int A, int C3) {
-  long long m = 0;
-  const long long rowsL[5] = {400LL * B, 81LL * B, 49LL * B, B, B};
-  const int Ks[5] = {256, 512, 576, 49 * C3, 512};
-  const int co[5] = {32, 64, C3, 512, A + 1};
-  for (int l = 0; l < 5; ++l) {
-    for (int mode : {ACMI_GEMM_F32, ACMI_GEMM_X3})
-      m = std::max(m, wgrad_plan(Ks[l], co[l], true, rowsL[l], false, mode).floats);
-    for (int mode : {ACMI_GEMM_F32, ACMI_GEMM_X3})
-      m = std::max(m, wgrad_plan(Ks[l], co[l], false, rowsL[l], l == 0, mode).floats);
-    // G factors of the same layer's output
-    if (co[l] <= 64) {  // (both Gram paths sized: gcov_layer picks by width)
-      int nc;
-      long long ch;
-      gram_plan(rowsL[l], &nc, &ch);
-      const long long np = co[l] <= 32 ? 32 : 64;
-      m = std::max(m, nc * (np + 1) * np);
-    }
-    m = std::max(m, gcov_plan(co[l], rowsL[l]).floats);
-  }
-  // band reductions of conv2 / conv3 (rows = images)
-  m = std::max(m, band_ws_floats(band_host_plan(20, 20, 32, 4, 4, 2, 64), B));
-  m = std::max(m, band_ws_floats(band_host_plan(9, 9, 64, 3, 3, 1, C3), B));
-  return (m + 63) / 64 * 64;
-}
-
-static long long afactor_ws_floats(int B) { return conv1_afactor_ws_ints(400LL * B); }
-
-// Workspace of acmi_backward / acmi_kfac_output_stats (one size for both):
-//   backward:      [scratch kBandScratch | conv1 A-factor ints | partials ...]
-//   output stats:  [scratch kBandScratch | sampled head gradients B x ldg | partials ...]
-// (prefixes rounded to 256 B); the partial region is the rest of the caller's
-// buffer, at least bwd_partial_floats
-static long long head_grad_ldg(int A) { return roundup4(A + 1) < 8 ? 8 : roundup4(A + 1); }
-static long long bwd_prefix_floats(int B) { return kBandScratch + (afactor_ws_floats(B) + 63) / 64 * 64; }
-static long long stats_prefix_floats(int B, int A) { return kBandScratch + ((long long)B * head_grad_ldg(A) + 63) / 64 * 64; }
-static int g_ws_flushes = 0;  // acmi_debug_ws_flushes
+namespace acmi {
 
 // Recorded on the backward's stream right after its input-gradient chain (per
 // device): acmi_stream_wait_backward_dx lets the sampled-loss chain on another
@@ -1614,56 +961,29 @@ static int backward_impl(const Layout& L, const float* P, const uint8_t* obs,
     if (rc0) return rc0;
   }
   // the conv1, heads and fc4 finalizes deferred into one launch: each layer's
-  // partials in their own range of the partial region (a layer that does not fit
-  // after the others finalizes the set so far first -- at workspaces near the
-  // minimum, acmi_debug_ws_flushes counts it)
-  WgradSet fin;
-  long long off = 0;
-  auto flush = [&]() {
-    if (fin.n) hipLaunchKernelGGL(finalize_wgrad_multi_kernel, dim3(fin.blocks), dim3(256), 0, s, fin);
-    fin = WgradSet();
-    off = 0;
-  };
+  // partials in their own range of the partial region
+  PartRanges<WgradSet> ra{part, avail, s};
   if (st && fuse_c1) {  // the conv1 weight gradient came with the A factor: reduce its chunks
     const long long rows = 400LL * B;
     WgradDesc d{wpart_c1, conv1_afactor_fused_chunks(rows), 256, 32, 0, 32, grads + L.off[0], 32,
                 nullptr, nullptr, (int)rows, 1.0f / 255.0f};
-    fin.add(d, 0, 0, fin_blocks(d));
+    ra.add(d, 0);
   }
-  // need: the layer's partial floats (its plan), checked here so that a layer
-  // that does not fit after the others starts a new range instead of failing;
-  // the layer then reports what it used, which must be that plan
-  auto layer = [&](long long need, auto&& run) -> int {
-    long long used = 0;
-    if (off > 0 && need > avail - off) ++g_ws_flushes, flush();
-    else if (fin.n + 2 > kWgradTasks) flush();
-    const int r = run(part + off, avail - off, &used);
-    ACMI_REQUIRE(r != ACMI_OK || used == need, ACMI_ERR_ARG,
-                 "internal: a layer used %lld partial floats against its planned %lld", used, need);
-    off += (used + 3) / 4 * 4;
-    return r;
-  };
   // heads: X = a4 (512), dY = dhead (A+1 columns: pi | v)
-  rc = layer(wgrad_plan(512, L.A + 1, st, B).floats, [&](float* pt, long long cap, long long* used) {
-    return wgrad_layer(DenseRows{a->a4, 512, B, 512}, 512, B, bw->dhead, bw->ldh, L.A + 1, st, pt, cap,
-                       grads + L.off[8], L.A, grads + L.off[10], st ? astat + L.stat_off[4] : nullptr, s, 0, 1.f,
-                       nullptr, nullptr, &fin, used);
-  });
+  rc = wgrad_layer(DenseRows{a->a4, 512, B, 512}, 512, B, bw->dhead, bw->ldh, L.A + 1, st, ra, grads + L.off[8],
+                   L.A, grads + L.off[10], st ? astat + L.stat_off[4] : nullptr);
   if (rc) return rc;
   // fc4: X = a3 flat; f16x2 with the prepared weights' a3 bound and max |d4|
   // (published by the dX chain's heads kernel)
   const unsigned* a3b =
       prep ? reinterpret_cast<const unsigned*>(prep + TowerPrep<C3>::HDR) + kTowMaxA3 : nullptr;
-  rc = layer(wgrad_plan(49 * C3, 512, st, B).floats, [&](float* pt, long long cap, long long* used) {
-    return wgrad_layer(DenseRows{a->a3, 49 * C3, B, 49 * C3}, 49 * C3, B, bw->d4, 512, 512, st, pt, cap,
-                       grads + L.off[6], 512, nullptr, st ? astat + L.stat_off[3] : nullptr, s, 0, 1.f, a3b,
-                       a3b ? bscr + kBsMaxD4 : nullptr, &fin, used);
-  });
+  rc = wgrad_layer(DenseRows{a->a3, 49 * C3, B, 49 * C3}, 49 * C3, B, bw->d4, 512, 512, st, ra, grads + L.off[6],
+                   512, nullptr, st ? astat + L.stat_off[3] : nullptr, 0, 1.f, a3b, a3b ? bscr + kBsMaxD4 : nullptr);
   if (rc) return rc;
-  flush();
+  ra.flush();
   // conv3 / conv2: pixel-pair band reductions over the dense activation rows
-  // (band.hpp), or the patches of a2 / a1
-  const long long band_cap = avail;
+  // (band.hpp, the whole partial region), or the patches of a2 / a1 (each
+  // patch-row layer's finalize launched straight after it)
   // a1 / a2 bounds from the weights (max |d2|, |d3| came with the dX chain): the
   // prepared weights' header holds them (tower_stats_body, the same sums as
   // band_bounds_kernel), else computed here
@@ -1674,29 +994,32 @@ static int backward_impl(const Layout& L, const float* P, const uint8_t* obs,
     if (!xb)
       hipLaunchKernelGGL(band_bounds_kernel, dim3(64), dim3(256), 0, s, P + L.off[0], P + L.off[1], P + L.off[2],
                          P + L.off[3], bscr);
-    rc = band_layer(a->a2, 9, 9, 64, 3, 3, 1, bw->d3, C3, B, part, band_cap, grads + L.off[4],
+    rc = band_layer(a->a2, 9, 9, 64, 3, 3, 1, bw->d3, C3, B, part, avail, grads + L.off[4],
                     astat + L.stat_off[2], 1.f, a2b, bscr + kBsMaxD3, s);
   } else
-    rc = wgrad_layer(ConvRows<float, 9, 9, 64, 3, 3, 1>{a->a2, 81 * 64, B * 49}, 576, 49LL * B,
-                     bw->d3, C3, C3, st, part, avail, grads + L.off[4], C3, nullptr,
-                     st ? astat + L.stat_off[2] : nullptr, s);
+    rc = wgrad_layer(ConvRows<float, 9, 9, 64, 3, 3, 1>{a->a2, 81 * 64, B * 49}, 576, 49LL * B, bw->d3, C3, C3, st,
+                     ra, grads + L.off[4], C3, nullptr, st ? astat + L.stat_off[2] : nullptr);
   if (rc) return rc;
+  ra.flush();
   if (band)
-    rc = band_layer(a->a1, 20, 20, 32, 4, 4, 2, bw->d2, 64, B, part, band_cap, grads + L.off[2],
+    rc = band_layer(a->a1, 20, 20, 32, 4, 4, 2, bw->d2, 64, B, part, avail, grads + L.off[2],
                     astat + L.stat_off[1], 1.f, a1b, bscr + kBsMaxD2, s, ACMI_PROF_CONV2_WGRAD);
   else
-    rc = wgrad_layer(ConvRows<float, 20, 20, 32, 4, 4, 2>{a->a1, 400 * 32, B * 81}, 512,
-                     81LL * B, bw->d2, 64, 64, st, part, avail, grads + L.off[2], 64, nullptr,
-                     st ? astat + L.stat_off[1] : nullptr, s, ACMI_PROF_CONV2_WGRAD);
+    rc = wgrad_layer(ConvRows<float, 20, 20, 32, 4, 4, 2>{a->a1, 400 * 32, B * 81}, 512, 81LL * B, bw->d2, 64, 64,
+                     st, ra, grads + L.off[2], 64, nullptr, st ? astat + L.stat_off[1] : nullptr,
+                     ACMI_PROF_CONV2_WGRAD);
   if (rc) return rc;
-  // conv1: patches of the u8 observations
-  // conv1: weight gradient on the f32 engine; its A factor from the u8 frames on
-  // the i8 matrix cores (exact integer sums, afactor_u8.hip)
+  ra.flush();
+  // conv1: weight gradient on the f32 engine from the raw u8 patches; its A factor
+  // from the u8 frames on the i8 matrix cores (exact integer sums, afactor_u8.hip)
   if (!fuse_c1)
-    rc = wgrad_layer(ConvRows<uint8_t, 84, 84, 4, 8, 8, 4>{obs, (uint32_t)img_stride, B * 400}, 256,
-                     400LL * B, bw->d1, 32, 32, false, part, avail, grads + L.off[0], 32, nullptr,
-                     nullptr, s, ACMI_PROF_CONV1_WGRAD, 1.0f / 255.0f);  // raw u8 patches
-  return rc;
+    rc = wgrad_layer(ConvRows<uint8_t, 84, 84, 4, 8, 8, 4>{obs, (uint32_t)img_stride, B * 400}, 256, 400LL * B,
+                     bw->d1, 32, 32, false, ra, grads + L.off[0], 32, nullptr, nullptr, ACMI_PROF_CONV1_WGRAD,
+                     1.0f / 255.0f);
+  if (rc) return rc;
+  ra.flush();
+  ACMI_LAUNCH_CHECK("wgrad_layer");
+  return ACMI_OK;
 }
 
 // sampled-loss output gradients at the heads (kfac "gradients" mode):
@@ -1759,46 +1082,29 @@ static int output_stats_impl(const Layout& L, const float* P, int B,
     g1_done = g1_fits && prep && g_gemm_mode == ACMI_GEMM_X3;  // (dx_conv2's Gram predicate)
   }
   // the G factors' finalizes deferred into one launch: every Gram's partials in
-  // their own range of the workspace (while they fit; else the set so far is
-  // finalized and the ranges start over)
-  CovSet fin;
-  long long off = 0;
-  auto flush = [&]() {
-    if (fin.n) hipLaunchKernelGGL(finalize_cov_multi_kernel, dim3(fin.blocks), dim3(256), 0, s, fin);
-    fin = CovSet();
-    off = 0;
-  };
-  if (g1_done) {  // G of conv1's output from the conv2 dX kernel's per-block Gram partials
-    fin.add(part, convt2_gram_blocks(B), 32, 32, gstat + L.stat_off[5 + 0], (int)(400LL * B), 1);
-    off = ((long long)convt2_gram_blocks(B) * 33 * 32 + 3) / 4 * 4;
+  // their own range of the workspace
+  PartRanges<CovSet> ra{part, cap, s};
+  if (g1_done) {  // G of conv1's output from the conv2 dX kernel's per-block Gram partials (the first range)
+    const int nc = convt2_gram_blocks(B);
+    const long long floats = (long long)nc * 33 * 32;
+    const float* g1_part = ra.begin(floats);
+    ra.add(g1_part, nc, 32, 32, gstat + L.stat_off[5 + 0], (int)(400LL * B), 1);
+    rc = ra.end(floats);
+    if (rc) return rc;
   }
-  // one Gram into the next free range, or -- when its plan's partials do not fit
-  // after the others -- into a new range after the set so far is finalized
-  auto gram = [&](const float* g, int ld, int n, long long rows, int sub, float* out, float* out_v, int vi,
-                  const unsigned* gmax) -> int {
-    long long used = 0;
-    const long long need = gcov_need(n, rows);
-    if (off > 0 && need > cap - off) ++g_ws_flushes, flush();
-    else if (fin.n + 2 > kCovTasks) flush();
-    const int r = gcov_layer(g, ld, n, rows, sub, part + off, cap - off, out, s, out_v, vi, gmax, &fin, &used);
-    ACMI_REQUIRE(r != ACMI_OK || used == need, ACMI_ERR_ARG,
-                 "internal: a Gram used %lld partial floats against its planned %lld", used, need);
-    off += (used + 3) / 4 * 4;
-    return r;
-  };
   // heads: G_pi (A x A) from the first A columns, G_v = element (A, A)
-  rc = gram(ghead, ldg, L.A + 1, B, L.A, gstat + L.stat_off[5 + 4], gstat + L.stat_off[5 + 5], L.A, nullptr);
+  rc = gcov_layer(ghead, ldg, L.A + 1, B, L.A, ra, gstat + L.stat_off[5 + 4], gstat + L.stat_off[5 + 5], L.A);
   if (rc) return rc;
   // (the dX chain above published max |d4| and max |d2| into dxs)
-  rc = gram(bw->d4, 512, 512, B, 512, gstat + L.stat_off[5 + 3], nullptr, -1, dxs + kBsMaxD4);
+  rc = gcov_layer(bw->d4, 512, 512, B, 512, ra, gstat + L.stat_off[5 + 3], nullptr, -1, dxs + kBsMaxD4);
   if (rc) return rc;
-  rc = gram(bw->d3, C3, C3, 49LL * B, C3, gstat + L.stat_off[5 + 2], nullptr, -1, nullptr);
+  rc = gcov_layer(bw->d3, C3, C3, 49LL * B, C3, ra, gstat + L.stat_off[5 + 2]);
   if (rc) return rc;
-  rc = gram(bw->d2, 64, 64, 81LL * B, 64, gstat + L.stat_off[5 + 1], nullptr, -1, dxs + kBsMaxD2);
+  rc = gcov_layer(bw->d2, 64, 64, 81LL * B, 64, ra, gstat + L.stat_off[5 + 1], nullptr, -1, dxs + kBsMaxD2);
   if (rc) return rc;
-  if (!g1_done) rc = gram(bw->d1, 32, 32, 400LL * B, 32, gstat + L.stat_off[5 + 0], nullptr, -1, nullptr);
+  if (!g1_done) rc = gcov_layer(bw->d1, 32, 32, 400LL * B, 32, ra, gstat + L.stat_off[5 + 0]);
   if (rc) return rc;
-  flush();
+  ra.flush();
   ACMI_LAUNCH_CHECK("G factor finalize");
   return ACMI_OK;
 }
@@ -2314,9 +1620,7 @@ int acmi_debug_convt2_form(int form) {
 }
 
 int acmi_debug_ws_flushes(void) {
-  const int n = g_ws_flushes;
-  g_ws_flushes = 0;
-  return n;
+  return g_ws_flushes.exchange(0);
 }
 
 int acmi_selftest_plans(int max_k) {

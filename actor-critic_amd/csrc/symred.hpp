@@ -16,7 +16,7 @@
 //   1 group  (0,0) (2,2) (4,4) (6,6)                    (diagonal slabs)
 // = 11 blocks per row chunk with every wave busy (vs 14).  Same staging,
 // fragment maps, MFMA chain order and split-K partial layout as gemm_kernel
-// (EpiPartial [chunk][I+1][J], column sums in row I), so finalize_wgrad_kernel
+// (EpiPartial [chunk][I+1][J], column sums in row I), so finalize_wgrad_body
 // is unchanged.  The column sums (the homogeneous row) of column slab b come
 // from the one wave whose row slab is 0 (sub-tile (0, b) is unique).
 #pragma once

@@ -17,7 +17,7 @@
 // v_mfma_f32_32x32x2_f32 (MI355X_MICROARCH.md constants table).
 //
 // Same slab plan (sym_plan), grid, staging loads, split-K partial layout and
-// column-sum contract as symred_kernel (symred.hpp), so finalize_wgrad_kernel is
+// column-sum contract as symred_kernel (symred.hpp), so finalize_wgrad_body is
 // shared.  What differs:
 //  * LDS image: per stage of BK = 16 k-rows, three parts (h, m, l), each
 //    [16 k][256 columns] of bf16 (512-byte rows) with 8-byte column slots

@@ -653,6 +653,70 @@ def test_band_backward_deterministic_and_symmetric(lib, cuda):
         assert torch.equal(F, F.t()), f
 
 
+def _update_stats_twice(lib, cuda, A, C3, B, seed=12):
+    """acmi_forward, acmi_backward with statistics and acmi_kfac_output_stats on
+    prepared weights, twice on the same seeded inputs (in the modes in effect):
+    [(grads, stats)] * 2 on the host, and the factor dims / offsets"""
+    params = rand_params(A, C3, cuda, seed=seed)
+    g = torch.Generator().manual_seed(seed + 1)
+    obs = torch.randint(0, 256, (B, 84, 84, 4), generator=g, dtype=torch.uint8).to(cuda)
+    prep = torch.empty(int(lib.acmi_conv_prep_bytes(C3)), dtype=torch.uint8, device=cuda)
+    net = _lib.Net(A, C3, params.data_ptr(), prep.data_ptr())
+    _lib.call('acmi_conv_prepare', ctypes.byref(net), _lib.ptr(prep), _lib.stream_handle())
+    ldh = (A + 1 + 3) // 4 * 4
+    dhead = torch.zeros(B, ldh)
+    dhead[:, :A + 1] = torch.randn(B, A + 1, generator=g) / B
+    dhead = dhead.to(cuda)
+    din, dout, so = (ctypes.c_int64 * 6)(), (ctypes.c_int64 * 6)(), (ctypes.c_int64 * 11)()
+    tot = ctypes.c_int64()
+    _lib.call('acmi_kfac_layout', A, C3, din, dout, so, ctypes.byref(tot))
+    need = int(lib.acmi_backward_ws_floats(B, A, C3))
+    nan = float('nan')
+    outs = []
+    for _ in range(2):
+        t, acts = alloc_acts(B, A, C3, cuda, masks=True)
+        d = [torch.full(sh, nan, device=cuda) for sh in ((B, 20, 20, 32), (B, 9, 9, 64), (B, 7, 7, C3), (B, 512))]
+        bwd = _lib.Bwd(*[x.data_ptr() for x in d], dhead.data_ptr(), ldh)
+        ws = torch.full((need,), nan, device=cuda)
+        grads = torch.full((params.numel(),), nan, device=cuda)
+        stats = torch.full((tot.value,), nan, device=cuda)
+        _lib.call('acmi_forward', ctypes.byref(net), _lib.ptr(obs), 84 * 84 * 4, B, ctypes.byref(acts), 1,
+                  _lib.stream_handle())
+        _lib.call('acmi_backward', ctypes.byref(net), _lib.ptr(obs), 84 * 84 * 4, B, ctypes.byref(acts),
+                  ctypes.byref(bwd), _lib.ptr(grads), _lib.ptr(stats), _lib.ptr(ws), need, _lib.stream_handle())
+        _lib.call('acmi_kfac_output_stats', ctypes.byref(net), B, ctypes.byref(acts), ctypes.byref(bwd), 7, 0, 3,
+                  _lib.ptr(stats), _lib.ptr(ws), need, _lib.stream_handle())
+        torch.cuda.synchronize()
+        outs.append((grads.cpu(), stats.cpu()))
+    return outs, list(din), list(dout), list(so)
+
+
+@pytest.mark.parametrize('conv_stats', ['band', 'patches'])
+@pytest.mark.parametrize('gemm', ['x3', 'f32'])
+@pytest.mark.parametrize('A,C3,B', [(4, 32, 24), (18, 64, 24), (4, 32, 100)])
+def test_update_factors_deterministic_and_symmetric(lib, cuda, A, C3, B, gemm, conv_stats):
+    """Every split-K finalize of the update, in each (gemm mode) x (conv-stats
+    mode) pair: two runs of forward, backward with statistics and output
+    statistics on the same inputs are bit-identical in gradients, A factors and
+    G factors (NaN-filled buffers: every entry is written, none is NaN), and
+    every A-factor and G-factor block equals its transpose exactly.  The shapes
+    reach each finalize body: an A x A head factor narrower than a tile and the
+    value element, the 64- and 512-wide tiled G factors, and at B = 100 conv1's
+    40 000 rows (more than 64 Gram chunks: a wave per element) and more than 8
+    chunks in the patch-row layers (the grouped gradient / A-factor body next to
+    the tiled A-factor body); off the band path the patch-row layers finalize
+    gradient and A factor as one two-task launch."""
+    gm = _lib.GEMM_X3 if gemm == 'x3' else _lib.GEMM_F32
+    cm = _lib.CONV_STATS_BAND if conv_stats == 'band' else _lib.CONV_STATS_PATCHES
+    outs, din, dout, so = _with_mode(lib, gm, _with_conv_stats, lib, cm, _update_stats_twice, lib, cuda, A, C3, B)
+    (g0, s0), (g1, s1) = outs
+    assert not torch.isnan(g0).any() and not torch.isnan(s0).any()
+    assert torch.equal(g0, g1) and torch.equal(s0, s1)
+    for i, n in enumerate(din[:5] + dout):  # A factors 0..4, then G factors 0..5
+        F = s0[so[i]:so[i] + n * n].reshape(n, n)
+        assert torch.equal(F, F.t()), ('A' if i < 5 else 'G', i % 5 if i < 5 else i - 5, n)
+
+
 def test_kfac_inverse_badly_conditioned(lib, cuda):
     """The pair sweep (two pivots per sweep, each 2 x 2 pivot block inverted in
     closed form, kfac.hip pivot_inverse) on damped factors of condition ~1e7:
