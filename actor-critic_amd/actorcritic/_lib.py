@@ -153,6 +153,13 @@ FWD_BF16 = 1  # one bf16 MFMA per product (BASELINE configs[4] "bf16 forward")
 CONV_STATS_PATCHES = 0  # acmi_set_conv_stats_mode: im2col patch rows
 CONV_STATS_BAND = 1     # pixel-pair band reduction (default)
 
+ERR_ARG = -1  # acmi_status_t ACMI_ERR_ARG
+
+# acmi_rollout_step (the fused rollout step) takes num_actions <= 31: its tail keeps
+# the A + 1 heads of one env in 32 floats of LDS (acmi.h); every other entry point
+# takes the whole 1..64 (agents.py steps wider action sets unfused)
+ROLLOUT_STEP_MAX_ACTIONS = 31
+
 PROF_CONV1_WGRAD = 1
 PROF_CONV2_WGRAD = 2
 PROF_CONV1_FWD = 3

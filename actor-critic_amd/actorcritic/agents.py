@@ -87,7 +87,10 @@ class _RolloutBuffers(object):
         need = int(_lib.load().acmi_forward_ws_floats(N // 2 if self.halves else N))
         self.ws = [torch.zeros(max(need, 1), dtype=torch.float32, device=dev) for _ in range(2)]
         self.use_graph = os.environ.get('ACMI_ROLLOUT_GRAPH', '0') == '1'
-        self.fused = os.environ.get('ACMI_ROLLOUT_FUSED', '1') != '0'
+        # the fused step (acmi_rollout_step) takes up to 31 actions; wider action sets
+        # step unfused: forward + sampler + env step, the ACMI_ROLLOUT_FUSED=0 path
+        self.fused = (os.environ.get('ACMI_ROLLOUT_FUSED', '1') != '0' and
+                      engine.A <= _lib.ROLLOUT_STEP_MAX_ACTIONS)
         # step fusion: step t's tail also runs step t+1's conv tower (needs the
         # fused tower: x3 gemm mode, checked once per rollout, and prepared weights)
         self.fuse_steps = self.fused and os.environ.get('ACMI_ROLLOUT_FUSE_STEPS', '1') != '0'

@@ -1404,9 +1404,13 @@ int acmi_rollout_step(const acmi_net_t* net, const uint8_t* obs, int64_t img_str
   const ModeScope mode_scope(net);
   ACMI_REQUIRE(io && io->actions && io->bad_rows && io->obs_out && io->rewards && io->terminals &&
                    io->episode_rewards && io->ld >= 1 && io->out_stride % 16 == 0 &&
-                   img_stride % 16 == 0 && io->row_offset >= 0 && net &&
-                   net->num_actions < kMaxHeads,
+                   img_stride % 16 == 0 && io->row_offset >= 0 && net,
                ACMI_ERR_ARG, "acmi_rollout_step: bad arguments");
+  ACMI_REQUIRE(net->num_actions < kMaxHeads, ACMI_ERR_ARG,
+               "acmi_rollout_step: num_actions=%d, the fused step takes at most %d (its tail holds the A + 1 heads "
+               "in %d floats of LDS); step wider action sets with acmi_forward_strided + acmi_sample_actions_dev + "
+               "acmi_env_step",
+               net->num_actions, kMaxHeads - 1, kMaxHeads);
   TailArgs ta{*io, obs, (long long)img_stride};
   return forward_dispatch(net, obs, img_stride, B, acts, 1, act_img_stride, stream, &ta);
 }

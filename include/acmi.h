@@ -355,7 +355,9 @@ int acmi_gather_rows(const uint8_t* obs, int64_t img_stride, int64_t src_rows,
  *   a_stats (nullable) <- for l = 0..4: A_l = mean over rows of [x;1][x;1]^T
  *           (conv: x = the (kh,kw,cin) input patch at every output location,
  *            rows = B*locations; fc: x = the input row; A_4 = fc4 output).
- * dhead: [B][ldh] from acmi_a2c_loss.  d1..d4 are [B]x(layer output) scratch.
+ * dhead: [B][ldh] from acmi_a2c_loss, ldh >= A+1 and a multiple of 4 (rows
+ * are read as float4; padding columns zero), else ACMI_ERR_ARG before anything
+ * is enqueued.  d1..d4 are [B]x(layer output) scratch.
  * ws: ws_floats >= acmi_backward_ws_floats(B, A, C3) floats; a smaller
  * ws_floats fails with ACMI_ERR_WS before anything is enqueued (nothing is
  * written).  Layout: [operand-scale scratch | conv1 A-factor integers |
@@ -597,7 +599,11 @@ int acmi_forward_strided(const acmi_net_t* net, const uint8_t* obs,
  * workgroup each) that finalises a4, computes the heads, samples the action
  * (acmi_sample_actions_dev semantics, row = io->row_offset + b) and steps the
  * env (acmi_env_step semantics, reading the same frames `obs`).  Bit-identical
- * to acmi_forward_strided + acmi_sample_actions_dev + acmi_env_step. */
+ * to acmi_forward_strided + acmi_sample_actions_dev + acmi_env_step.
+ * Takes net->num_actions <= 31 only (the fused kernel keeps the A + 1 heads of
+ * its env in 32 floats of LDS): 32..64 actions fail with ACMI_ERR_ARG before
+ * anything is enqueued; step those with the three calls above, which take the
+ * whole 1..64 (MultiEnvAgent does). */
 typedef struct acmi_rollout_io {
   uint32_t seed, stream_id, counter; /* sampler RNG key                      */
   const uint32_t* counter_dev;       /* nullable: counter += *counter_dev     */

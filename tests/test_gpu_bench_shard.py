@@ -15,6 +15,10 @@ G from the sampled head gradients of oracle.sampled_head_grads).
 
 Tolerances (max-abs error over max-abs value, per block): gradients and A factors
 2e-5, G factors 5e-5 -- the section 5 bounds of the small-size tests.
+
+_stats_vs_float64 is the float64 harness of these tests and of
+test_gpu_layout_matrix.py, which runs it over the (A, C3) domain, the per-net modes
+and the batch edges.
 """
 import ctypes
 import os
@@ -75,7 +79,7 @@ class _Ref(object):
         a3 = torch.relu(p3 @ w3.reshape(-1, self.C3) + b3).reshape(-1, 7, 7, self.C3)
         a3f = a3.reshape(a3.shape[0], -1)
         a4 = torch.relu(a3f @ w4 + b4)
-        return [p1, p2, p3, a3f, a4], (a1, a2, a3, a4)
+        return [p1, p2, p3, a3f, a4], (a1, a2, a3, a4, a4 @ wp + bp, (a4 @ wv + bv)[:, 0])
 
     def _chain(self, masks, dlogits, dvalue):
         w1, b1, w2, b2, w3, b3, w4, b4, wp, bp, wv, bv = self.w
@@ -94,15 +98,16 @@ class _Ref(object):
         x = obs.to(self.dt) / 255.0
         return [_patches(x, 8, 4), _patches(a1, 4, 2), _patches(a2, 3, 1), a3.reshape(a3.shape[0], -1), a4]
 
-    def add(self, obs, gpu_acts, dlogits, dvalue, g_pi, g_v, gpu_inputs=False):
+    def add(self, obs, gpu_acts, dlogits, dvalue, g_pi, g_v, gpu_inputs=False, ins=None):
         """gpu_acts: the kernel forward's f32 a1..a4 of these images, whose ReLU
         masks the chains use: a pre-activation within f32 rounding of 0 may have
         the other sign in float64, and at 10240 rows such flips (one whole term of
         a cancelling sum each) would dominate the comparison of the backward's
         arithmetic.  The forward itself is compared with float64 elsewhere.
         gpu_inputs: take the layer inputs from gpu_acts too (else the float64
-        forward's)."""
-        ins = self._inputs(obs, gpu_acts) if gpu_inputs else self._forward(obs)[0]
+        forward's, or `ins` where the caller has run _forward(obs) already)."""
+        if ins is None:
+            ins = self._inputs(obs, gpu_acts) if gpu_inputs else self._forward(obs)[0]
         ins = ins + [ins[4]]
         masks = [(a > 0).to(self.dt) for a in gpu_acts]
         douts = self._chain(masks, dlogits, dvalue)
@@ -127,49 +132,75 @@ def _rel(got, ref):
     return ((got.double() - ref).abs().max() / ref.abs().max()).item()
 
 
-def _stats_vs_float64(lib, cuda, B, params, seed=2024):
+FWD_NAMES = ('a1', 'a2', 'a3', 'a4', 'logits', 'value')
+
+
+def _stats_vs_float64(lib, cuda, B, params, seed=2024, A=4, C3=32, use_prep=True, masks=True, gemm_mode=None,
+                      forward_mode=None, conv_stats_mode=None, ldh=None, fill=0.0, zero_refs=None):
     """One acmi_forward + acmi_backward (loss gradients + A factors) + one
-    acmi_kfac_output_stats (G factors of the sampled losses) over B images, each
-    block against float64 (and against plain float32 arithmetic of the same
-    formulas): {(kind, block): (kernel rel err, plain-f32 rel err)}."""
+    acmi_kfac_output_stats (G factors of the sampled losses) over B images of an
+    (A, C3) net, each block against float64 (and against plain float32 arithmetic
+    of the same formulas): {(kind, block): (kernel rel err, plain-f32 rel err)},
+    kind 'grad' (12 blocks), 'A' (5), 'G' (6) and 'fwd' (FWD_NAMES: the forward's
+    a1..a4, logits and value against the float64 forward).
+
+    use_prep: prepared weights (acmi_conv_prepare) or none; masks: the forward
+    writes the ReLU' mask words m1..m3; gemm_mode / forward_mode / conv_stats_mode:
+    per-net modes (acmi_net_t holds mode + 1), None the process default; ldh: the
+    head gradients' row stride (A + 1 rounded up to 4); fill: what the workspace,
+    gradients, statistics and d1..d4 hold before the calls (NaN shows an entry left
+    unwritten).  A block whose float64 reference is identically zero has no
+    relative error: its key is appended to zero_refs (None: there must be none) and
+    its kernel error is 0 when the GPU block is exactly zero, inf otherwise."""
     from actorcritic._engine import Layout
-    A, C3 = 4, 32
     L = Layout(A, C3)
     gen = torch.Generator(device=cuda).manual_seed(seed)
     obs = torch.randint(0, 256, (B, 84, 84, 4), generator=gen, device=cuda, dtype=torch.uint8)
     z = lambda *s: torch.zeros(*s, dtype=torch.float32, device=cuda)
+    full = lambda *s: torch.full(s, fill, dtype=torch.float32, device=cuda)
     t = dict(a1=z(B, 20, 20, 32), a2=z(B, 9, 9, 64), a3=z(B, 7, 7, C3), a4=z(B, 512), logits=z(B, A), value=z(B))
-    acts = _lib.Acts(*[t[k].data_ptr() for k in ('a1', 'a2', 'a3', 'a4', 'logits', 'value')], A)
-    zi = lambda *s: torch.zeros(*s, dtype=torch.int32, device=cuda)  # the production path's ReLU' masks
-    t.update(m1=zi(B, 400), m2=zi(B, 162), m3=zi(B, 49 * C3 // 32))
-    acts.m1, acts.m2, acts.m3 = t['m1'].data_ptr(), t['m2'].data_ptr(), t['m3'].data_ptr()
-    prep = torch.empty(int(lib.acmi_conv_prep_bytes(C3)), dtype=torch.uint8, device=cuda)
-    net = _lib.Net(A, C3, params.data_ptr(), prep.data_ptr())
+    acts = _lib.Acts(*[t[k].data_ptr() for k in FWD_NAMES], A)
+    if masks:  # the production path's ReLU' masks
+        zi = lambda *s: torch.zeros(*s, dtype=torch.int32, device=cuda)
+        t.update(m1=zi(B, 400), m2=zi(B, 162), m3=zi(B, 49 * C3 // 32))
+        acts.m1, acts.m2, acts.m3 = t['m1'].data_ptr(), t['m2'].data_ptr(), t['m3'].data_ptr()
+    prep = torch.empty(int(lib.acmi_conv_prep_bytes(C3)), dtype=torch.uint8, device=cuda) if use_prep else None
+    mode = lambda m: 0 if m is None else m + 1
+    net = _lib.Net(A, C3, params.data_ptr(), prep.data_ptr() if use_prep else None, mode(gemm_mode),
+                   mode(forward_mode), mode(conv_stats_mode))
     st = _lib.stream_handle()
-    _lib.call('acmi_conv_prepare', ctypes.byref(net), _lib.ptr(prep), st)
+    if use_prep:
+        _lib.call('acmi_conv_prepare', ctypes.byref(net), _lib.ptr(prep), st)
     _lib.call('acmi_forward', ctypes.byref(net), _lib.ptr(obs), 84 * 84 * 4, B, ctypes.byref(acts), 1, st)
     # head gradients shaped like the A2C loss's (a2c_loss: mean over M rows)
-    ldh = 8
+    ldh = (A + 1 + 3) // 4 * 4 if ldh is None else ldh
     dhead = z(B, ldh)
     dhead[:, :A + 1] = torch.randn(B, A + 1, generator=gen, device=cuda) / B
     din = (ctypes.c_int64 * 6)()
     so = (ctypes.c_int64 * 11)()
     tot = ctypes.c_int64()
     _lib.call('acmi_kfac_layout', A, C3, din, None, so, ctypes.byref(tot))
-    ws = z(int(lib.acmi_backward_ws_floats(B, A, C3)))
-    d = [z(B, 20, 20, 32), z(B, 9, 9, 64), z(B, 7, 7, C3), z(B, 512)]
+    ws = full(int(lib.acmi_backward_ws_floats(B, A, C3)))
+    d = [full(B, 20, 20, 32), full(B, 9, 9, 64), full(B, 7, 7, C3), full(B, 512)]
     bwd = _lib.Bwd(*[x.data_ptr() for x in d], dhead.data_ptr(), ldh)
-    grads, astat, gstat = z(params.numel()), z(tot.value), z(tot.value)
+    grads, astat, gstat = full(params.numel()), full(tot.value), full(tot.value)
     _lib.call('acmi_backward', ctypes.byref(net), _lib.ptr(obs), 84 * 84 * 4, B, ctypes.byref(acts),
               ctypes.byref(bwd), _lib.ptr(grads), _lib.ptr(astat), _lib.ptr(ws), ws.numel(), st)
-    ds = [z(B, 20, 20, 32), z(B, 9, 9, 64), z(B, 7, 7, C3), z(B, 512)]
+    ds = [full(B, 20, 20, 32), full(B, 9, 9, 64), full(B, 7, 7, C3), full(B, 512)]
     dhead_s = z(B, ldh)  # the sampled chain writes its own head gradients here
     bwd_s = _lib.Bwd(*[x.data_ptr() for x in ds], dhead_s.data_ptr(), ldh)
     seed_s, counter = 0x4b464143, 41
     _lib.call('acmi_kfac_output_stats', ctypes.byref(net), B, ctypes.byref(acts), ctypes.byref(bwd_s), seed_s, 0,
               counter, _lib.ptr(gstat), _lib.ptr(ws), ws.numel(), st)
     torch.cuda.synchronize()
-    assert torch.isfinite(grads).all() and torch.isfinite(astat).all() and torch.isfinite(gstat).all()
+    ends = L.offsets[1:] + [L.nparams]
+    nf = list(din)[:5] + [32, 64, C3, 512, A, 1]  # the 11 factors' widths
+    assert torch.isfinite(grads).all(), [b for b, (o, e) in enumerate(zip(L.offsets, ends))
+                                         if not torch.isfinite(grads[o:e]).all()]
+    for f in range(5):  # (the statistics buffers hold A factors in astat, G factors in gstat)
+        assert torch.isfinite(astat[so[f]:so[f] + nf[f] ** 2]).all(), ('A', f)
+    for l in range(6):
+        assert torch.isfinite(gstat[so[5 + l]:so[5 + l] + nf[5 + l] ** 2]).all(), ('G', l)
 
     # the sampled head gradients from the kernel's own f32 logits and counters
     g_pi, g_v, _ = oracle.sampled_head_grads(t['logits'].cpu().numpy(), seed_s, 0, counter)
@@ -179,24 +210,43 @@ def _stats_vs_float64(lib, cuda, B, params, seed=2024):
     ref32 = _Ref(L.split(params), A, C3, cuda, torch.float32)
     dh64 = dhead.double()
     chunk = 1024
+    # the forward: max |GPU - float64| and max |plain f32 - float64| over the chunks
+    fwd_max = {k: [0.0, 0.0, 0.0] for k in FWD_NAMES}
     for i in range(0, B, chunk):
         j = min(B, i + chunk)
+        outs = {}
         for r in (ref, ref32):
+            ins, outs[r] = r._forward(obs[i:j])
             r.add(obs[i:j], [t[k][i:j] for k in ('a1', 'a2', 'a3', 'a4')], dh64[i:j, :A].to(r.dt),
-                  dh64[i:j, A].to(r.dt), g_pi[i:j].to(r.dt), g_v[i:j].to(r.dt))
+                  dh64[i:j, A].to(r.dt), g_pi[i:j].to(r.dt), g_v[i:j].to(r.dt), ins=ins)
+        for k, o64, o32 in zip(FWD_NAMES, outs[ref], outs[ref32]):
+            m = fwd_max[k]
+            m[0] = max(m[0], (t[k][i:j].double().reshape(o64.shape) - o64).abs().max().item())
+            m[1] = max(m[1], (o32.double() - o64).abs().max().item())
+            m[2] = max(m[2], o64.abs().max().item())
     g_ref, a_ref, gf_ref = ref.result()
     g_32, a_32, gf_32 = ref32.result()
 
+    def rel(key, got, r64, r32):
+        if r64.abs().max().item() == 0.0:
+            assert zero_refs is not None, (key, 'the float64 reference is identically zero')
+            zero_refs.append(key)
+            return (0.0 if not got.any().item() else float('inf'), 0.0)
+        return (_rel(got, r64), _rel(r32, r64))
+
     errs = {}
-    ends = L.offsets[1:] + [L.nparams]
     for blk, (o, e) in enumerate(zip(L.offsets, ends)):
-        errs[('grad', blk)] = (_rel(grads[o:e], g_ref[o:e]), _rel(g_32[o:e], g_ref[o:e]))
+        errs[('grad', blk)] = rel(('grad', blk), grads[o:e], g_ref[o:e], g_32[o:e])
     for f in range(5):
         n = din[f]
-        errs[('A', f)] = (_rel(astat[so[f]:so[f] + n * n].reshape(n, n), a_ref[f]), _rel(a_32[f], a_ref[f]))
+        errs[('A', f)] = rel(('A', f), astat[so[f]:so[f] + n * n].reshape(n, n), a_ref[f], a_32[f])
     for l in range(6):
         n = gf_ref[l].shape[0]
-        errs[('G', l)] = (_rel(gstat[so[5 + l]:so[5 + l] + n * n].reshape(n, n), gf_ref[l]), _rel(gf_32[l], gf_ref[l]))
+        errs[('G', l)] = rel(('G', l), gstat[so[5 + l]:so[5 + l] + n * n].reshape(n, n), gf_ref[l], gf_32[l])
+    for k in FWD_NAMES:
+        e_gpu, e_32, m = fwd_max[k]
+        assert m > 0, ('fwd', k)
+        errs[('fwd', k)] = (e_gpu / m, e_32 / m)
     for k, (v, v32) in errs.items():
         print(k, 'kernel %.2e  plain f32 %.2e' % (v, v32))
     return errs

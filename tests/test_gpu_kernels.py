@@ -1067,12 +1067,14 @@ def test_conv1_afactor_and_weight_gradient_match_float64(lib, cuda, B):
         assert rel < 1e-6, rel
 
 
-def test_kfac_pack_unpack_round_trip(lib, cuda):
+@pytest.mark.parametrize('A,C3', [(4, 32), (1, 32), (33, 32), (64, 64)])
+def test_kfac_pack_unpack_round_trip(lib, cuda, A, C3):
     """acmi_kfac_pack / unpack (the data-parallel all-reduce of the factor statistics
     as upper triangles): the packed A and G parts are the factors' upper triangles
     row by row, back to back, and unpacking restores symmetric factors bit for bit
-    (and mirrors the upper triangle into the lower one)."""
-    A, C3 = 4, 32
+    (and mirrors the upper triangle into the lower one) -- at the ACKTR layout, a
+    1 x 1 policy block, an odd 33-wide one and the widest layout (3137-wide fc4 A
+    factor, 64 x 64 policy block)."""
     din = (ctypes.c_int64 * 6)()
     dout = (ctypes.c_int64 * 6)()
     so = (ctypes.c_int64 * 11)()

@@ -6,6 +6,8 @@ against the float64 oracle from the GPU's own optimizer state.
 Layouts (A, C3): (4, 32) the ACKTR config; (18, 32) the full action set; (6, 64) a
 six-action game (the narrow first product with inv_ld = 8) on the wide tower, whose
 fc4 A factor is 3137 x 3137 (np = 3168: 99 pivot steps of the block Gauss-Jordan).
+The step also runs at the ends of the action range: (1, 32) a 1 x 1 policy block,
+(33, 32) the narrow product at dout = 33 (inv_ld = 36), (64, 64) the widest one.
 
 Scalars passed to the library as float are rounded to f32 in the references first
 (1 - decay and damping / CONV_LOCATIONS[l] are formed in f32, as the kernels do).
@@ -22,8 +24,8 @@ from test_gpu_parity import _blocks, _build, _feed, oracle
 
 pytestmark = pytest.mark.gpu
 
-LAYOUTS = [(4, 32), (18, 32), (6, 64)]
-LAYOUT_IDS = ['a4-c32', 'a18-c32', 'a6-c64']
+LAYOUTS = [(4, 32), (18, 32), (6, 64), (1, 32), (33, 32), (64, 64)]
+LAYOUT_IDS = ['a4-c32', 'a18-c32', 'a6-c64', 'a1-c32', 'a33-c32', 'a64-c64']
 EPS = 2.0 ** -24  # one f32 rounding, relative
 F32 = np.float32
 
@@ -393,6 +395,13 @@ def test_step_precon_coeff_and_apply_match_float64(lib, cuda, A, C3):
       fc4          8.2e-7/3.5e-7 | 1.7e-6/5.9e-7   8.2e-7/3.5e-7 | 1.5e-6/7.5e-7   1.1e-6/3.6e-7 | 2.3e-6/6.1e-7
       fc_policy    4.2e-7/4.2e-7 | 7.0e-7/7.0e-7   1.2e-7/2.9e-7 | 1.7e-7/4.1e-7   9.8e-8/4.2e-7 | 1.5e-7/6.2e-7
       fc_baseline  8.1e-8/2.1e-7 | 7.4e-8/2.5e-7   8.8e-8/2.2e-7 | 1.1e-7/3.5e-7   8.7e-8/2.0e-7 | 1.4e-7/3.5e-7
+      block        (1, 32)                         (33, 32)                        (64, 64)
+      conv1        3.0e-7/2.2e-7 | 5.4e-7/2.5e-7   3.2e-7/2.4e-7 | 4.6e-7/3.1e-7   2.9e-7/2.3e-7 | 3.8e-7/2.8e-7
+      conv2        4.4e-7/2.9e-7 | 6.7e-7/4.6e-7   4.4e-7/2.8e-7 | 5.1e-7/3.4e-7   4.4e-7/2.8e-7 | 8.5e-7/4.0e-7
+      conv3        4.3e-7/2.7e-7 | 6.1e-7/4.2e-7   4.4e-7/2.8e-7 | 5.1e-7/2.9e-7   4.5e-7/2.8e-7 | 7.5e-7/4.7e-7
+      fc4          8.2e-7/3.5e-7 | 1.6e-6/6.9e-7   8.2e-7/3.5e-7 | 1.7e-6/8.6e-7   1.1e-6/3.5e-7 | 2.0e-6/7.6e-7
+      fc_policy    8.0e-8/2.2e-7 | 8.8e-8/3.9e-7   1.3e-7/2.7e-7 | 2.3e-7/3.6e-7   4.3e-7/2.8e-7 | 6.0e-7/5.3e-7
+      fc_baseline  9.8e-8/2.3e-7 | 1.5e-7/3.8e-7   8.4e-8/2.1e-7 | 9.5e-8/3.0e-7   8.4e-8/1.8e-7 | 1.1e-7/2.1e-7
     (the f32-CPU figures depend on the host's BLAS; the worst ratio is fc4 at
     (6, 64), 3.8x in max-abs, K = 3137 in the first product)."""
     case = _step_case(A, C3)

@@ -366,9 +366,86 @@ def test_rollout_matches_oracle_env_and_tower(lib, cuda):
         np.testing.assert_array_equal(act[:, t].cpu().numpy(), oracle.sample_f32(lg[:, t], u))
 
 
+@pytest.mark.parametrize('A', [31, 32, 64])
+def test_rollout_either_side_of_the_fused_step_head_limit(lib, cuda, monkeypatch, A):
+    """MultiEnvAgent.interact around acmi_rollout_step's limit of 31 actions (its tail
+    keeps the A + 1 heads of an env in 32 floats of LDS): A = 31 fills them exactly
+    and runs the fused step; A = 32 and A = 64 step unfused (forward, sampler, env
+    step: the ACMI_ROLLOUT_FUSED=0 path) -- the stepper, the sampler and the tower
+    against the oracle as in test_rollout_matches_oracle_env_and_tower."""
+    from actorcritic import session as sess
+    monkeypatch.delenv('ACMI_ROLLOUT_FUSED', raising=False)
+    N, T = 6, 4
+    env, model, agent, obj, gs, opt, op, params = _build(N, T, A)
+    with sess.Session() as s:
+        data = agent.interact(s)
+    assert agent._bufs.fused == (A <= 31)
+    obs, act, rew, term, nxt, infos = [x for x in data]
+    o = obs.cpu().numpy()
+    act_h = act.cpu().numpy()
+    assert act_h.min() >= 0 and act_h.max() < A
+    if A == 64:
+        assert act_h.max() >= 32  # the draws reach the actions past the fused step's limit
+    envs = [oracle.SyntheticAtari(5, e) for e in range(N)]
+    for e in range(N):
+        np.testing.assert_array_equal(o[e, 0], envs[e].reset())
+        for t in range(T):
+            ob, r, d, ep = envs[e].step(int(act_h[e, t]))
+            nxt_ref = ob
+            if t + 1 < T:
+                np.testing.assert_array_equal(o[e, t + 1], ob)
+            assert float(rew[e, t]) == r and bool(term[e, t]) == d
+        np.testing.assert_array_equal(nxt[e].cpu().numpy(), nxt_ref)
+    fwd = model.engine.lookup_rollout(obs)
+    ref = oracle.forward(params, o.reshape(-1, 84, 84, 4), A, 32)
+    for name, got in (('logits', fwd.flat_logits), ('value', fwd.flat_value)):
+        r = ref[name].reshape(got.shape)
+        rel = np.abs(got.cpu().double().numpy() - r).max() / np.abs(r).max()
+        assert rel < 1e-5, (name, rel)
+    lg = fwd.flat_logits.cpu().numpy().reshape(N, T, A)
+    for t in range(T):
+        u = oracle.sample_uniforms(3, 0, t, N)
+        np.testing.assert_array_equal(act_h[:, t], oracle.sample_f32(lg[:, t], u))
+
+
+def test_rollout_step_refuses_32_actions(lib, cuda):
+    """acmi_rollout_step itself at A = 32, called as the agent's fused step 0 would:
+    ACMI_ERR_ARG with a message that names the limit, and nothing enqueued -- the
+    sentinel-filled outputs (actions, rewards, terminals, episode rewards, the next
+    stacks, logits, values, a4) are unchanged after a synchronise."""
+    import ctypes
+    from actorcritic import session as sess
+    from actorcritic.agents import OBS_BYTES
+    N, T, A = 6, 4, 32
+    env, model, agent, obj, gs, opt, op, params = _build(N, T, A)
+    with sess.Session() as s:
+        agent.interact(s)  # (unfused) sizes the rollout buffers and leaves next_obs
+    eng, benv, rb = model.engine, env.batched, agent._bufs
+    torch.cuda.synchronize()
+    outs = [rb.actions, rb.rewards, rb.terminals, rb.episode_rewards, rb.obs, rb.acts.logits, rb.acts.value,
+            rb.acts.a4]
+    for x in outs:
+        x.fill_(7)
+    acts = rb.acts.view(0, T, ws_rows=N)
+    io = _lib.RolloutIO(3, 0, 0, None, 0, rb.actions.data_ptr(), eng._bad_rows.data_ptr(), benv.range_state(0),
+                        benv.env_offset, benv.seed, rb.obs.data_ptr() + OBS_BYTES, T * OBS_BYTES,
+                        rb.rewards.data_ptr(), rb.terminals.data_ptr(), rb.episode_rewards.data_ptr(), T, 0, None, T,
+                        rb.obs.data_ptr())
+    rc = lib.acmi_rollout_step(ctypes.byref(eng.net()), ctypes.c_void_p(rb.next_obs.data_ptr()), OBS_BYTES, N,
+                               ctypes.byref(acts), T, ctypes.byref(io), eng.stream())
+    torch.cuda.synchronize()
+    assert rc == _lib.ERR_ARG, rc
+    msg = lib.acmi_last_error().decode()
+    assert 'num_actions=32' in msg and 'at most 31' in msg, msg
+    for x in outs:
+        assert (x == 7).all()
+
+
 _UPDATE_CASES = [
     # (N, T, A, games, forward)
     (3, 5, 4, None, 'f32'),
+    (3, 5, 33, None, 'f32'),  # a narrow 33-wide policy block (kfac_narrow_kernel at dout = 33), unfused rollout
+    (3, 5, 64, None, 'f32'),  # the widest policy block
     (32, 20, 4, None, 'f32'),
     (32, 20, 18, 'atari57', 'f32'),
     (32, 20, 18, 'atari57', 'bf16'),
@@ -391,7 +468,8 @@ def _blocks(A, C3):
 
 
 @pytest.mark.parametrize('N,T,A,games,fwd', _UPDATE_CASES,
-                         ids=['toy', 'configs2-32x20', 'configs4-a18-atari57', 'configs4-a18-atari57-bf16fwd'])
+                         ids=['toy', 'toy-a33', 'toy-a64', 'configs2-32x20', 'configs4-a18-atari57',
+                              'configs4-a18-atari57-bf16fwd'])
 def test_acktr_update_matches_oracle(lib, cuda, forward_mode, N, T, A, games, fwd):
     """One steady-state ACKTR update at gs=40 (covariance update + inverse + apply)
     against the float64 oracle on the same rollout -- at a toy size, at the
@@ -405,7 +483,11 @@ def test_acktr_update_matches_oracle(lib, cuda, forward_mode, N, T, A, games, fw
     A = 18 runs the policy head's categorical G factor at 18 x 18
     (policies.py:146-158), the heads' weight gradient + A factor with 19 dY columns,
     and the K-FAC step's narrow first product for A % 4 != 0 (kfac.hip
-    kfac_narrow_kernel).  The bf16 case runs the rollout tower on bf16 MFMAs
+    kfac_narrow_kernel).  The toy cases at A = 33 and A = 64 (15 rows, rolled out
+    unfused: past the fused step's 31 actions) run a whole update through the engine
+    with a narrow odd-width and the widest policy block: the heads' wide Gram
+    (np = 36, 68), the narrow product at dout = 33 and the 64-wide grouped one.
+    The bf16 case runs the rollout tower on bf16 MFMAs
     (BASELINE configs[4] "bf16 forward / fp32 KFAC"); the update behind it is f32.
 
     The oracle's backward, factors and step are fed the GPU's own forward --
