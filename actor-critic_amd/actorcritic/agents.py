@@ -5,8 +5,10 @@ layout.  With a batched device env and an :class:`AtariModel` it runs the whole
 T-step rollout on the GPU: per step one strided tower forward that writes its
 activations straight into the update's [N*T] buffers (row n*T + t), one sampling
 kernel, one stepper kernel that writes the next stacked frame into the [N, T+1]
-observation buffer — no host copies, no Python lists.  Anything else takes the
-reference's list-based loop.
+observation buffer — no host copies, no Python lists.  Host-stepped envs behind a
+HostAtariEnvs adaptor keep the same device buffers (_interact_host): the envs step on
+the host between the sampler and one frame kernel that writes the next stacks.  Anything
+else takes the reference's list-based loop.
 
 Two opt-in variants, bit-identical to the one-chain rollout (test_two_stream_rollout_
 is_bit_identical, and across updates test_rollout_variants_give_identical_updates):
@@ -96,6 +98,20 @@ class _RolloutBuffers(object):
         self.fuse_steps = self.fused and os.environ.get('ACMI_ROLLOUT_FUSE_STEPS', '1') != '0'
         self.graph, self.graph_key, self.warm = None, None, False
         self.ctr_dev = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.host = None  # _HostRolloutBuffers, made by the first host-stepped rollout
+
+
+class _HostRolloutBuffers(object):
+    """What a rollout over host-stepped envs adds to _RolloutBuffers."""
+
+    def __init__(self, dev, N, T):
+        # row t: the N actions of step t, then that step's count of non-finite logit rows
+        self.act_bad = torch.zeros((T, N + 1), dtype=torch.int32, device=dev)
+        self.act_bad_host = torch.zeros(N + 1, dtype=torch.int32, pin_memory=True)
+        self.event = torch.cuda.Event()
+        self.rewards = torch.zeros((N, T), dtype=torch.float32, pin_memory=True)
+        self.terminals = torch.zeros((N, T), dtype=torch.uint8, pin_memory=True)
+        self.episode_rewards = torch.zeros((N, T), dtype=torch.float32, pin_memory=True)
 
 
 class MultiEnvAgent(Agent):
@@ -202,14 +218,14 @@ class MultiEnvAgent(Agent):
         eng.sample_counter += T
 
     def _interact_device(self):
-        from actorcritic.envs.atari.model import ForwardOut
-        from actorcritic.envs.atari.wrappers import EpisodeInfoBatch
         eng = self._model.engine
         env = self._env.batched
         N, T = env.num_envs, self._num_steps
         if self._bufs is None or self._bufs.N != N or self._bufs.T != T:
             self._bufs = _RolloutBuffers(eng, N, T)
         rb = self._bufs
+        if getattr(env, 'host_stepped', False):
+            return self._interact_host(eng, env, rb, N, T)
         if rb.bad_event is not None:  # deferred NaN-logit check of the previous rollout
             t_wait = time.perf_counter()
             rb.bad_event.synchronize()
@@ -247,6 +263,59 @@ class MultiEnvAgent(Agent):
         rb.bad_host.copy_(eng._bad_rows, non_blocking=True)
         rb.bad_event = torch.cuda.Event()
         rb.bad_event.record()
+        return self._batch(eng, rb, N, T)
+
+    def _interact_host(self, eng, env, rb, N, T):
+        """The device rollout over host-stepped envs (HostAtariEnvs): per step one strided
+        forward into the update's activation rows, one sampling kernel, ONE host wait (the
+        D2H of the N actions and the bad-row counter), the envs' host step, and one upload
+        + acmi_atari_rollout_frames launch that writes the next stacks into obs[:, t+1].
+        Rewards / terminals / episode rewards gather in pinned [N, T] arrays and are
+        uploaded once.  The fused step, graph capture and the two-halves split of the
+        synthetic stepper do not apply: one chain, any action count."""
+        if rb.host is None:
+            rb.host = _HostRolloutBuffers(eng.device, N, T)
+        hb = rb.host
+        if self._observations is None:
+            env.reset_into(rb.next_obs.data_ptr())
+        A = eng.A
+        stream = eng.stream()
+        obs0 = rb.obs.data_ptr()
+        seed = (self._model._random_seed or 0) & 0xFFFFFFFF
+        rb.obs[:, 0].copy_(rb.next_obs)
+        hb.act_bad.zero_()
+        rewards, terminals, episode_rewards = hb.rewards.numpy(), hb.terminals.numpy(), hb.episode_rewards.numpy()
+        for t in range(T):
+            src = obs0 + t * OBS_BYTES
+            eng.forward(src, N, rb.acts.view(t, T), want_value=True, img_stride=T * OBS_BYTES, act_stride=T)
+            row = hb.act_bad[t]  # [actions of step t (N) | rows with non-finite logits (1)]
+            _lib.call('acmi_sample_actions_at', _lib.c_vp(rb.acts.logits.data_ptr() + 4 * t * A), T * A, N, A,
+                      seed, 0, eng.sample_counter & 0xFFFFFFFF, eng.rank * N, None, 0, _lib.c_vp(row.data_ptr()),
+                      _lib.c_vp(row.data_ptr() + 4 * N), stream)
+            eng.sample_counter += 1
+            hb.act_bad_host.copy_(row, non_blocking=True)
+            hb.event.record()
+            hb.event.synchronize()  # the step's only host wait
+            got = hb.act_bad_host.numpy()
+            if got[N] != 0:  # no env sees an action of -1
+                eng._bad_rows += int(got[N])
+                eng.check_bad_rows()
+            rewards[:, t], terminals[:, t], episode_rewards[:, t] = env.host_step(got[:N])
+            if t + 1 < T:
+                dst, dstride = src + OBS_BYTES, T * OBS_BYTES
+            else:
+                dst, dstride = rb.next_obs.data_ptr(), OBS_BYTES
+            env.stack_into(src, T * OBS_BYTES, dst, dstride)
+        rb.actions.copy_(hb.act_bad[:, :N].t())
+        rb.rewards.copy_(hb.rewards, non_blocking=True)
+        rb.terminals.copy_(hb.terminals, non_blocking=True)
+        rb.episode_rewards.copy_(hb.episode_rewards, non_blocking=True)
+        return self._batch(eng, rb, N, T)
+
+    def _batch(self, eng, rb, N, T):
+        """interact()'s 6-tuple from the rollout buffers, registered for the update."""
+        from actorcritic.envs.atari.model import ForwardOut
+        from actorcritic.envs.atari.wrappers import EpisodeInfoBatch
         self._observations = rb.next_obs
         out = (rb.obs, rb.actions, rb.rewards, rb.terminals.view(torch.bool), rb.next_obs, rb.episode_rewards)
         if self._copy:

@@ -8,8 +8,10 @@ reference semantics (np.roll then zero-fill on a terminal, wrappers.py:224-230),
 lazily at the step after a terminal (multi_env.py:127-132: the reset observation is
 never emitted), and tracks the EpisodeInfoWrapper total reward (wrappers.py:263-294).
 
-Real ALE emulation and the frame preprocessing wrappers (wrappers.py:16-198) are out of
-the hot-path scope.
+Real ALE emulation is out of scope; the reference's wrapper chain
+around an ALE-like env is below, and :class:`HostAtariEnvs` puts a batch of such host
+envs on the device rollout path: they step on the host, their raw frames are
+preprocessed and stacked on the device (acmi_atari_rollout_frames).
 """
 
 import ctypes
@@ -260,7 +262,8 @@ class SyntheticAtariEnvs(object):
 # (wrappers.py:16-260, assembled by make_atari_env, a2c_acktr.py:175-213).  The
 # control-flow wrappers are host objects with the reference's semantics; the frame
 # arithmetic (gray + INTER_AREA resize, frame stacking) runs on the device through
-# acmi_atari_preprocess / acmi_atari_stack, batched in AtariFramePipeline.
+# acmi_atari_preprocess / acmi_atari_stack, batched in AtariFramePipeline, and for a
+# rollout through acmi_atari_rollout_frames in HostAtariEnvs.
 # ---------------------------------------------------------------------------
 RAW_HEIGHT, RAW_WIDTH = 210, 160
 
@@ -344,6 +347,146 @@ class AtariFramePipeline(object):
     def step(self, terminals=None):
         """FrameStackWrapper.step of every env: roll, zero where terminal, insert."""
         return self._launch(terminals, False)
+
+
+def plan_host_step(terminated):
+    """Slots of one auto-reset step of N host envs (no GPU involved).
+
+    ``terminated[n]``: env n's previous step ended its episode, so it resets before it
+    steps (_AutoResetWrapper.step, multi_env.py:127-132).  Returns (step_slot [N] int32,
+    reset_slot [N] int32, K): the step frames take slots 0..N-1 of the upload, the K
+    reset frames are packed after them in env order (slots N..N+K-1), -1 = no reset."""
+    terminated = np.asarray(terminated, dtype=bool)
+    N = terminated.shape[0]
+    step_slot = np.arange(N, dtype=np.int32)
+    reset_slot = np.full(N, -1, np.int32)
+    K = int(terminated.sum())
+    reset_slot[terminated] = N + np.arange(K, dtype=np.int32)
+    return step_slot, reset_slot, K
+
+
+class HostAtariEnvs(object):
+    """A batch of host-stepped Atari envs behind the device rollout: N gym-like envs that
+    return RAW RGB [H, W, 3] u8 frames (``wrap_atari_env(env, preprocess=False)`` chains,
+    or SubprocessEnvs around them), stepped by a thread pool; their frames go to the GPU
+    in one pinned copy per step and acmi_atari_rollout_frames turns them into the stacked
+    observations where the rollout wants them.
+
+    The adaptor is the auto-reset (_AutoResetWrapper, multi_env.py:121-137) and the frame
+    stack (FrameStackWrapper, wrappers.py:201-235) of every env: the envs it takes are
+    wrapped in neither.  ``MultiEnv`` recognises it by ``host_stepped``.
+    """
+
+    host_stepped = True
+
+    def __init__(self, envs, height=RAW_HEIGHT, width=RAW_WIDTH, device=None):
+        import concurrent.futures
+        self.device = _device_of(device)
+        self._envs = list(envs)
+        self.num_envs = N = len(self._envs)
+        if N == 0:
+            raise ValueError('HostAtariEnvs needs at least one env')
+        self.height, self.width = int(height), int(width)
+        self.observation_space = spaces.Box(low=0, high=255, shape=(84, 84, 4), dtype=np.uint8)
+        self.action_space = self._envs[0].action_space
+        # the threads block on the envs' pipes (SubprocessEnv): one per env, as MultiEnv
+        self._executor = concurrent.futures.ThreadPoolExecutor(N)
+        self._terminated = np.zeros(N, bool)
+        # one staging buffer: [step_slot i32[N] | reset_slot i32[N] | terminals u8[N] | pad]
+        # [frame slot 0 .. 2N-1]; a step uploads the metadata and its N + K frames
+        self._frame_bytes = self.height * self.width * 3
+        self._meta_bytes = (9 * N + 15) // 16 * 16
+        total = self._meta_bytes + 2 * N * self._frame_bytes
+        self._host = torch.empty(total, dtype=torch.uint8).pin_memory()
+        self._dev = torch.empty(total, dtype=torch.uint8, device=self.device)
+        h = self._host.numpy()
+        self._step_slot = h[:4 * N].view(np.int32)
+        self._reset_slot = h[4 * N:8 * N].view(np.int32)
+        self._terminals = h[8 * N:9 * N]
+        self._frames = h[self._meta_bytes:].reshape(2 * N, self.height, self.width, 3)
+        self._nslots = 0
+        self._uploaded = torch.cuda.Event()  # after the last upload: the staging buffer is free again
+        self._obs = None
+
+    def host_step(self, actions):
+        """Resets the envs whose previous step was terminal, steps every env and fills the
+        staging buffer.  -> (rewards f32[N], terminals bool[N], episode_rewards f32[N],
+        NaN where no episode ended), numpy."""
+        N = self.num_envs
+        actions = np.asarray(actions).reshape(N)
+        step_slot, reset_slot, K = plan_host_step(self._terminated)
+        self._uploaded.synchronize()
+        rewards = np.zeros(N, np.float32)
+        terminals = np.zeros(N, bool)
+        episode_rewards = np.full(N, np.nan, np.float32)
+
+        def one(n):
+            env = self._envs[n]
+            if reset_slot[n] >= 0:
+                np.copyto(self._frames[reset_slot[n]], env.reset())
+            frame, reward, terminal, info = env.step(int(actions[n]))
+            np.copyto(self._frames[step_slot[n]], frame)
+            rewards[n], terminals[n] = reward, terminal
+            if info and 'episode' in info:
+                episode_rewards[n] = info['episode']['total_reward']
+
+        list(self._executor.map(one, range(N)))
+        self._step_slot[:], self._reset_slot[:], self._terminals[:] = step_slot, reset_slot, terminals
+        self._nslots = N + K
+        self._terminated = terminals
+        return rewards, terminals, episode_rewards
+
+    def stack_into(self, stack_in_ptr, in_stride, stack_out_ptr, out_stride):
+        """Uploads what host_step staged (metadata + N + K frames, one copy) and makes the
+        next stacks: stack_in + n*in_stride -> stack_out + n*out_stride."""
+        N = self.num_envs
+        nbytes = self._meta_bytes + self._nslots * self._frame_bytes
+        self._dev[:nbytes].copy_(self._host[:nbytes], non_blocking=True)
+        self._uploaded.record(torch.cuda.current_stream(self.device))
+        base = self._dev.data_ptr()
+        _lib.call('acmi_atari_rollout_frames', ctypes.c_void_p(base + self._meta_bytes), self._frame_bytes,
+                  self._nslots, self.height, self.width, N, ctypes.c_void_p(base), ctypes.c_void_p(base + 4 * N),
+                  ctypes.c_void_p(base + 8 * N), ctypes.c_void_p(stack_in_ptr) if stack_in_ptr else None,
+                  in_stride, ctypes.c_void_p(stack_out_ptr), out_stride, None, _lib.stream_handle(self.device))
+
+    def reset_into(self, obs_ptr, stride=OBS_BYTES):
+        """Resets every env; its first observation [f,f,f,f] at obs_ptr + n*stride."""
+        N = self.num_envs
+        self._uploaded.synchronize()
+
+        def one(n):
+            np.copyto(self._frames[n], self._envs[n].reset())
+
+        list(self._executor.map(one, range(N)))
+        self._step_slot[:], self._reset_slot[:], self._terminals[:] = -1, np.arange(N), 0
+        self._nslots = N
+        self._terminated = np.zeros(N, bool)
+        self.stack_into(None, 0, obs_ptr, stride)
+
+    # -- gym-like batched API (as SyntheticAtariEnvs) ---------------------------
+    def reset(self):
+        if self._obs is None:
+            self._obs = torch.zeros((self.num_envs, 84, 84, 4), dtype=torch.uint8, device=self.device)
+        self.reset_into(self._obs.data_ptr())
+        return self._obs.clone()
+
+    def step(self, actions):
+        """actions: [N] ints -> (obs [N,84,84,4] u8, rewards [N], terminals [N] bool, EpisodeInfoBatch)."""
+        if self._obs is None:
+            raise ValueError('step() before reset()')
+        if isinstance(actions, torch.Tensor):
+            actions = actions.cpu().numpy()
+        rewards, terminals, episode_rewards = self.host_step(actions)
+        p = self._obs.data_ptr()
+        self.stack_into(p, OBS_BYTES, p, OBS_BYTES)
+        dev = lambda a: torch.from_numpy(a).to(self.device)
+        return self._obs.clone(), dev(rewards), dev(terminals), EpisodeInfoBatch(dev(episode_rewards)[:, None])
+
+    def close(self):
+        for env in self._envs:
+            if hasattr(env, 'close'):
+                self._executor.submit(env.close)
+        self._executor.shutdown()
 
 
 class AtariPreprocessFrameWrapper(ObservationWrapper):
@@ -500,7 +643,8 @@ class AtariInfoClearWrapper(Wrapper):
 def wrap_atari_env(env, render=False, preprocess=True, device=None):
     """The make_atari_env chain (a2c_acktr.py:190-213) around an ALE-like env (step ->
     (frame, reward, terminal, {'ale.lives': ...}), unwrapped.np_random).  With
-    preprocess=False the frames stay raw RGB, for a batched AtariFramePipeline."""
+    preprocess=False the frames stay raw RGB, for the batched HostAtariEnvs (the device
+    rollout) or an AtariFramePipeline."""
     env = AtariNoopResetWrapper(env, noop_max=30)
     env = AtariFrameskipWrapper(env, frameskip=4)
     if preprocess:
@@ -514,10 +658,11 @@ def wrap_atari_env(env, render=False, preprocess=True, device=None):
     return AtariInfoClearWrapper(env)
 
 
-def make_atari_env(env_id, render=False, device=None):
-    """a2c_acktr.py:175-213: gym.make(env_id) wrapped with the Atari chain."""
+def make_atari_env(env_id, render=False, preprocess=True, device=None):
+    """a2c_acktr.py:175-213: gym.make(env_id) wrapped with the Atari chain
+    (preprocess=False: raw RGB frames, for HostAtariEnvs)."""
     try:
         import gym
     except ImportError as e:  # not in this image; ALE emulation is out of scope (DESIGN.md §8)
         raise ImportError('make_atari_env needs gym with the Atari (ALE) environments') from e
-    return wrap_atari_env(gym.make(env_id), render=render, device=device)
+    return wrap_atari_env(gym.make(env_id), render=render, preprocess=preprocess, device=device)

@@ -22,13 +22,20 @@ from actorcritic.session import Session, get_or_create_global_step, no_op
 
 
 def train_a2c_acktr(acktr, env_id, num_envs, num_steps, checkpoint_path, model_name, summary_path=None,
-                    max_updates=None, seed=0, log_every=10):
+                    max_updates=None, seed=0, log_every=10, env_fns=None):
     """Trains an Atari model with A2C (RMSProp, conv3 64) or ACKTR (K-FAC, conv3 32).
 
     ``num_envs`` is per GPU; with WORLD_SIZE > 1 (torchrun) every rank steps its own shard.
+    ``env_fns``: None (the synthetic batched stepper) or one function per env of this rank
+    that makes a host env with raw RGB frames (create_host_environments); ``num_envs`` is
+    then their number.
     """
     parallel.init_from_env()
-    multi_env = MultiEnv(create_environments(env_id, num_envs, seed=seed))
+    if env_fns is not None:
+        multi_env = create_host_environments(env_fns)
+        num_envs = multi_env.num_envs
+    else:
+        multi_env = MultiEnv(create_environments(env_id, num_envs, seed=seed))
 
     conv3_num_filters = 32 if acktr else 64
     model = AtariModel(multi_env.observation_space, multi_env.action_space, conv3_num_filters, random_seed=seed)
@@ -93,6 +100,16 @@ def create_environments(env_id, num_envs, seed=0):
     """The batched synthetic Atari stepper for this rank's env shard."""
     return wrappers.SyntheticAtariEnvs(num_envs, num_actions=wrappers.num_actions_for(env_id), seed=seed,
                                        env_offset=parallel.rank() * num_envs)
+
+
+def create_host_environments(env_fns, subprocess=True):
+    """Host-stepped envs on the device rollout path: each function makes a gym-like env
+    that returns raw RGB frames (``wrappers.make_atari_env(env_id, preprocess=False)``, or
+    ``wrappers.wrap_atari_env(ale_like, preprocess=False)``), in a process of its own
+    (``subprocess``: the functions must be picklable) or in this one."""
+    from actorcritic.multi_env import create_subprocess_envs
+    envs = create_subprocess_envs(env_fns) if subprocess else [env_fn() for env_fn in env_fns]
+    return MultiEnv(wrappers.HostAtariEnvs(envs))
 
 
 def create_optimizer(acktr, model, learning_rate):

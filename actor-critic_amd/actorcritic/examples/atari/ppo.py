@@ -18,7 +18,8 @@ import actorcritic.envs.atari.wrappers as wrappers
 from actorcritic import checkpoint, parallel
 from actorcritic.agents import MultiEnvAgent
 from actorcritic.envs.atari.model import AtariModel
-from actorcritic.examples.atari.a2c_acktr import create_environments, load_model, save_model
+from actorcritic.examples.atari.a2c_acktr import (create_environments, create_host_environments, load_model,
+                                                   save_model)
 from actorcritic.multi_env import MultiEnv
 from actorcritic.nn import AdamOptimizer, ClipGlobalNormOptimizer, linear_decay
 from actorcritic.objectives import PPOObjective
@@ -27,7 +28,7 @@ from actorcritic.session import Session, get_or_create_global_step, no_op
 
 def train_ppo(env_id, num_envs, num_steps, checkpoint_path, model_name, summary_path=None, max_updates=None, seed=0,
               log_every=10, num_epochs=4, num_minibatches=4, clip_range=0.1, value_clip_range=None,
-              minibatch='envs'):
+              minibatch='envs', env_fns=None):
     """Trains an Atari model (conv3 64) with PPO.
 
     ``num_envs`` is per GPU; with WORLD_SIZE > 1 (torchrun) every rank steps its own shard.
@@ -35,9 +36,16 @@ def train_ppo(env_id, num_envs, num_steps, checkpoint_path, model_name, summary_
     ``num_envs``) or 'rows' (the usual PPO minibatches: per epoch, a permutation of all
     ``num_envs * num_steps`` rows cut into ``num_minibatches`` parts, which must divide that
     product; costs a second copy of the batch's observations on the device).
+    ``env_fns``: None (the synthetic batched stepper) or one function per env of this rank that
+    makes a host env with raw RGB frames (a2c_acktr.create_host_environments); ``num_envs`` is
+    then their number.
     """
     parallel.init_from_env()
-    multi_env = MultiEnv(create_environments(env_id, num_envs, seed=seed))
+    if env_fns is not None:
+        multi_env = create_host_environments(env_fns)
+        num_envs = multi_env.num_envs
+    else:
+        multi_env = MultiEnv(create_environments(env_id, num_envs, seed=seed))
 
     model = AtariModel(multi_env.observation_space, multi_env.action_space, 64, random_seed=seed)
     agent = MultiEnvAgent(multi_env, model, num_steps)

@@ -3,6 +3,10 @@
 ``MultiEnv(envs)`` accepts either
   * a batched device env (:class:`actorcritic.envs.atari.wrappers.SyntheticAtariEnvs`):
     the hot path — one kernel steps every env, observations never leave HBM; or
+  * a batched adaptor over host envs that return raw frames
+    (:class:`actorcritic.envs.atari.wrappers.HostAtariEnvs`, marked ``host_stepped``):
+    the envs step on the host, the frames are preprocessed and stacked on the device
+    and the rollout stays on the device path; or
   * a list of gym-like envs: the reference's semantics (each wrapped in an
     auto-reset wrapper, stepped through a ThreadPoolExecutor, ``None`` actions skip an
     env), for CPU-hosted environments, typically :class:`SubprocessEnv` instances from
@@ -48,7 +52,7 @@ class _AutoResetWrapper(object):
 
 class MultiEnv(object):
     def __init__(self, envs):
-        if hasattr(envs, 'step_into'):
+        if hasattr(envs, 'step_into') or getattr(envs, 'host_stepped', False):
             self._batched = envs
             self._envs = None
             self._executor = None
@@ -59,7 +63,8 @@ class MultiEnv(object):
 
     @property
     def batched(self):
-        """The batched device env, or None for a list of host envs."""
+        """The batched env (device stepper or host-stepped adaptor), or None for a list of
+        host envs."""
         return self._batched
 
     @property

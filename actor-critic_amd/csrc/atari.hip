@@ -235,10 +235,187 @@ int atari_launch(const char* what, const uint8_t* raw, int64_t env_stride, int64
   return ACMI_OK;
 }
 
+// ---------------------------------------------------------------------------
+// Rollout form (acmi_atari_rollout_frames): per env up to two frames picked by slot
+// out of one upload, _AutoResetWrapper.step over FrameStackWrapper.reset/step
+// (multi_env.py:121-137, wrappers.py:224-235) in one launch.  Same grid, same LDS
+// band, same float arithmetic as atari_frames_kernel; an env with a reset frame
+// passes both frames through the band in turn, an env with no frame copies its stack.
+// ---------------------------------------------------------------------------
+
+// gray rows of one frame (groups g0 .. g0+ng-1 of 4 pixels) into an LDS band
+__device__ __forceinline__ void stage_gray_band(const uint32_t* f, int g0, int ng, int tid, uint8_t* gray) {
+  for (int base = 0; base < ng; base += kAtariThreads * kUnroll) {
+    uint32_t a[kUnroll][3];
+#pragma unroll
+    for (int u = 0; u < kUnroll; ++u) {
+      const int g = base + tid + u * kAtariThreads;
+      const int gs = g0 + (g < ng ? g : 0);
+#pragma unroll
+      for (int q = 0; q < 3; ++q) a[u][q] = f[3 * gs + q];
+    }
+#pragma unroll
+    for (int u = 0; u < kUnroll; ++u) {
+      const int g = base + tid + u * kAtariThreads;
+      if (g >= ng) break;
+      reinterpret_cast<uint32_t*>(gray)[g] = gray4(a[u][0], a[u][1], a[u][2]);
+    }
+  }
+}
+
+// one destination pixel from a gray band whose row 0 is source row r0: the sums of
+// atari_frames_kernel's resampling loop, in its order
+template <int NY, int NX, int KX>
+__device__ __forceinline__ uint32_t area_pixel(const uint8_t* gray, int W, int r0, int nrows, const AreaRun& ry,
+                                               const int (&xo)[KX], const float (&xa)[KX], int nx) {
+  constexpr int KY = NY ? NY : kMaxTab;
+  const int ny = NY ? NY : ry.count;
+  float sum = 0.f;
+#pragma unroll
+  for (int j = 0; j < KY; ++j) {
+    if (j >= ny) break;
+    const uint8_t* row = gray + min(ry.first + j - r0, nrows - 1) * W;
+    float buf = 0.f;
+#pragma unroll
+    for (int k = 0; k < KX; ++k) {
+      if (k >= nx) break;
+      buf = __fadd_rn(buf, __fmul_rn((float)row[xo[k]], xa[k]));
+    }
+    sum = __fadd_rn(sum, __fmul_rn(ry.alpha[j], buf));
+  }
+  return (uint32_t)min(255, max(0, __float2int_rn(sum)));
+}
+
+template <int NY, int NX>
+__global__ __launch_bounds__(kAtariThreads) void atari_rollout_kernel(
+    const uint8_t* frames, long long frame_stride, long long nslots, int H, int W, double scale_y,
+    double scale_x, const int32_t* step_slot, const int32_t* reset_slot,
+    const uint8_t* terminals, const uint8_t* stack_in, long long in_stride, uint8_t* out,
+    long long out_stride, int32_t* bad_envs) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  AreaRun* ytab = reinterpret_cast<AreaRun*>(smem);
+  AreaRun* xtab = ytab + kBandRows;
+  uint8_t* rpix = reinterpret_cast<uint8_t*>(xtab + kOut);  // the band's reset-frame pixels
+  uint8_t* gray = rpix + kBandRows * kOut;
+  const int band = blockIdx.x, e = blockIdx.y, tid = threadIdx.x;
+  const int dy0 = band * kBandRows;
+  constexpr int kBandWords = kBandRows * kOut;
+
+  // everything below branches on per-env (workgroup-uniform) values only
+  const int ss = step_slot[e], rs = reset_slot[e];
+  const bool step = ss >= 0, reset = rs >= 0;
+  const bool term = step && terminals != nullptr && terminals[e] != 0;
+  const bool needs_in = reset ? false : !term;  // rows 1 (no terminal) and 4 of the table
+  uint32_t* dst = reinterpret_cast<uint32_t*>(out + e * out_stride) + dy0 * kOut;
+  const uint32_t* sin =
+      stack_in ? reinterpret_cast<const uint32_t*>(stack_in + e * in_stride) + dy0 * kOut : nullptr;
+
+  // a slot past the upload (or a stack that is needed and was not given): nothing is
+  // read, the env's stack is zero and it is counted once
+  if (ss >= nslots || rs >= nslots || (needs_in && sin == nullptr)) {
+    for (int p = tid; p < kBandWords; p += kAtariThreads) dst[p] = 0u;
+    if (band == 0 && tid == 0 && bad_envs != nullptr) atomicAdd(bad_envs, 1);
+    return;
+  }
+  if (!step && !reset) {  // env not stepped
+    if (sin != dst)
+      for (int p = tid; p < kBandWords; p += kAtariThreads) dst[p] = sin[p];
+    return;
+  }
+
+  if (tid < kBandRows) area_run(H, dy0 + tid, scale_y, &ytab[tid]);
+  else if (tid >= 64 && tid < 64 + kOut) area_run(W, tid - 64, scale_x, &xtab[tid - 64]);
+  int r0, r1;
+  {
+    AreaRun ra, rb;
+    area_run(H, dy0, scale_y, &ra);
+    area_run(H, dy0 + kBandRows - 1, scale_y, &rb);
+    r0 = ra.first;
+    r1 = rb.first + rb.count - 1;
+  }
+  const int g0 = r0 * W / 4, ng = (r1 - r0 + 1) * W / 4, nrows = r1 - r0 + 1;
+  constexpr int kRowGroups = kAtariThreads / kOut;
+  constexpr int KX = NX ? NX : kMaxTab;
+  const int dx = tid % kOut, ly0 = tid / kOut;
+  const bool owner = ly0 < kRowGroups;  // (the other threads only stage)
+  int nx, xo[KX];
+  float xa[KX];
+  auto load_x_run = [&]() {  // (the tables are in LDS after the first barrier)
+    const AreaRun& rx = xtab[dx];
+    nx = NX ? NX : rx.count;
+#pragma unroll
+    for (int k = 0; k < KX; ++k) {
+      xo[k] = min(rx.first + k, W - 1);  // padded entries (weight 0) stay inside the row
+      xa[k] = rx.alpha[k];
+    }
+  };
+
+  // the reset frame first: its pixels wait in rpix (each read back by the thread that
+  // wrote it) while the step frame takes over the band.  A second band instead would
+  // cost the eighth workgroup of a CU (160 KB / 21.8 KB)
+  if (reset) {
+    stage_gray_band(reinterpret_cast<const uint32_t*>(frames + rs * frame_stride), g0, ng, tid, gray);
+    __syncthreads();
+    if (owner) {
+      load_x_run();
+      for (int ly = ly0; ly < kBandRows; ly += kRowGroups) {
+        const int p = ly * kOut + dx;
+        const uint32_t y = area_pixel<NY, NX, KX>(gray, W, r0, nrows, ytab[ly], xo, xa, nx);
+        if (step) rpix[p] = (uint8_t)y;
+        else dst[p] = y * 0x01010101u;  // [R,R,R,R]
+      }
+    }
+    if (!step) return;
+    __syncthreads();  // every thread is done with the reset frame's band
+  }
+  stage_gray_band(reinterpret_cast<const uint32_t*>(frames + ss * frame_stride), g0, ng, tid, gray);
+  __syncthreads();
+  if (!owner) return;
+  if (!reset) load_x_run();
+  for (int ly = ly0; ly < kBandRows; ly += kRowGroups) {
+    const int p = ly * kOut + dx;
+    // (the stack word's load is issued ahead of the pixel's arithmetic, not behind it)
+    const uint32_t old = reset || term ? 0u : sin[p];
+    const uint32_t y = area_pixel<NY, NX, KX>(gray, W, r0, nrows, ytab[ly], xo, xa, nx);
+    const uint32_t prev = reset && !term ? rpix[p] * 0x01010101u : old;
+    dst[p] = (prev >> 8) | (y << 24);
+  }
+}
+
 }  // namespace
 }  // namespace acmi
 
 extern "C" {
+
+int acmi_atari_rollout_frames(const uint8_t* frames, int64_t frame_stride, int64_t nslots, int H, int W,
+                              int N, const int32_t* step_slot, const int32_t* reset_slot,
+                              const uint8_t* terminals, const uint8_t* stack_in, int64_t in_stride,
+                              uint8_t* stack_out, int64_t out_stride, int32_t* bad_envs,
+                              acmi_stream_t stream) {
+  using namespace acmi;
+  constexpr int64_t kStack = 4 * kOut * kOut;
+  const bool int_ratio = H % kOut == 0 && W % kOut == 0;
+  const bool shape_ok = H >= kOut && W >= kOut && H <= 6 * kOut && W <= 6 * kOut && W % 4 == 0 &&
+                        H * W <= 40960 && !int_ratio;
+  const bool frames_ok = frames && (uintptr_t)frames % 4 == 0 && frame_stride % 4 == 0 && nslots >= 0 &&
+                         (!shape_ok || frame_stride >= (int64_t)H * W * 3);
+  const bool out_ok = stack_out && (uintptr_t)stack_out % 4 == 0 && out_stride % 4 == 0 && out_stride >= kStack;
+  const bool in_ok = !stack_in || ((uintptr_t)stack_in % 4 == 0 && in_stride % 4 == 0 && in_stride >= kStack &&
+                                   (stack_in != stack_out || in_stride == out_stride));
+  ACMI_REQUIRE(shape_ok && frames_ok && out_ok && in_ok && N >= 0 && N <= 65535 && step_slot && reset_slot,
+               ACMI_ERR_ARG, "acmi_atari_rollout_frames: bad arguments");
+  if (N == 0) return ACMI_OK;
+  const double sy = 1.0 / ((double)kOut / H), sx = 1.0 / ((double)kOut / W);
+  const int band_rows = std::min(H, (int)(kBandRows * sy) + 3);
+  const size_t lds = (kBandRows + kOut) * sizeof(AreaRun) + kBandRows * kOut + (size_t)band_rows * W;
+  const bool fixed3 = area_max_run(H) <= 3 && area_max_run(W) <= 3;
+  auto kern = fixed3 ? atari_rollout_kernel<3, 3> : atari_rollout_kernel<0, 0>;
+  hipLaunchKernelGGL(kern, dim3(kBands, N), dim3(kAtariThreads), lds, (hipStream_t)stream, frames,
+                     (long long)frame_stride, (long long)nslots, H, W, sy, sx, step_slot, reset_slot,
+                     terminals, stack_in, (long long)in_stride, stack_out, (long long)out_stride, bad_envs);
+  ACMI_LAUNCH_CHECK("acmi_atari_rollout_frames");
+  return ACMI_OK;
+}
 
 int acmi_atari_preprocess(const uint8_t* raw, int64_t env_stride, int64_t frame_stride,
                           const uint8_t* nframes, int N, int H, int W, uint8_t* gray_out,

@@ -583,6 +583,33 @@ int acmi_atari_stack(const uint8_t* raw, int64_t env_stride, int64_t frame_strid
                      const uint8_t* nframes, int N, int H, int W,
                      const uint8_t* terminals, int reset, const uint8_t* stack_in,
                      uint8_t* stack_out, int64_t stack_stride, acmi_stream_t stream);
+/* The rollout form for host-stepped envs: _AutoResetWrapper.step over
+ * FrameStackWrapper.reset/step (multi_env.py:121-137, wrappers.py:224-235) of N
+ * envs in one launch.  `frames` holds nslots raw [H][W][3] u8 frames, slot s at
+ * frames + s*frame_stride (frame_stride >= H*W*3; one frame each: the host
+ * chain has already max-pooled the skipped pair).  step_slot / reset_slot:
+ * device int32[N], negative = absent; terminals: device u8[N], nullable.
+ * With G / R the gray + INTER_AREA of frames step_slot[n] / reset_slot[n]
+ * (acmi_atari_preprocess's arithmetic), env n's stack word p becomes
+ *   step  reset   out[p]
+ *   >= 0  <  0    (term ? 0 : in[p] >> 8) | G << 24
+ *   >= 0  >= 0    (term ? 0 : (R*0x01010101) >> 8) | G << 24   reset, then step
+ *   <  0  >= 0    R*0x01010101                                 the first reset
+ *   <  0  <  0    in[p]                                        env not stepped
+ * stack_in + n*in_stride -> stack_out + n*out_stride; stack_in == stack_out
+ * needs equal strides, otherwise the stacks read and written must not overlap.
+ * stack_in may be NULL when no env reads it (rows 2, 3, and row 1 on a
+ * terminal).  An env with a slot >= nslots reads nothing: its stack is zero and
+ * *bad_envs (device int, nullable, accumulated) counts it once; so is an env
+ * that needs stack_in when it is NULL.  Shapes and alignment as above, for
+ * frames, both stacks and all three strides; N <= 65535. */
+int acmi_atari_rollout_frames(const uint8_t* frames, int64_t frame_stride,
+                              int64_t nslots, int H, int W, int N,
+                              const int32_t* step_slot, const int32_t* reset_slot,
+                              const uint8_t* terminals, const uint8_t* stack_in,
+                              int64_t in_stride, uint8_t* stack_out,
+                              int64_t out_stride, int32_t* bad_envs,
+                              acmi_stream_t stream);
 
 /* Rollout variant of acmi_forward: batch row b reads image b of `obs` and
  * writes activation row b*act_img_stride (env-major [N][T] buffers, the
