@@ -683,8 +683,9 @@ int acmi_rollout_step(const acmi_net_t* net, const uint8_t* obs,
  * ---------------------------------------------------------------------- */
 /* Host-only self-check of the GEMM launch planners (no GPU needed): the
  * slab groups of the fused wgrad/A-factor reduction cover every needed
- * sub-tile and column sum for K = 64..max_k, split-K chunks cover the rows.
- * Returns 0, or the first failing K (-1: chunk plan). */
+ * sub-tile and column sum for K = 64..max_k, split-K chunks cover the rows,
+ * the forward's fc4 split counts all have a compiled heads / tail kernel.
+ * Returns 0, or the first failing K (-1: chunk plan, -3000: fc4 split counts). */
 int acmi_selftest_plans(int max_k);
 /* Host-only diagnostic: the number of times acmi_backward / acmi_kfac_output_stats
  * finalized their deferred small-layer set early because the next layer's

@@ -470,6 +470,50 @@ def test_forward_matches_torch(lib, cuda, A, C3, B):
         assert rel < 1e-5, (name, rel)
 
 
+def _forward_split_count_errors(lib, cuda, B, nz, gemm):
+    """a4 / logits / value of the first and last 8 rows of a B-image forward with the
+    forward workspace attached, relative to float64 on those 16 images"""
+    A, C3 = 4, 32
+    if gemm == 'x3':  # the case is the split count it claims (fc4's slabs, [nz][B + 1][512], lead the workspace)
+        assert lib.acmi_forward_ws_floats(B) // ((B + 1) * 512) == nz
+    params = rand_params(A, C3, cuda, seed=5)
+    g = torch.Generator(device=cuda).manual_seed(6)
+    obs = torch.randint(0, 256, (B, 84, 84, 4), generator=g, dtype=torch.uint8, device=cuda)
+    t, acts = alloc_acts(B, A, C3, cuda, masks=True)
+    for k in ('a1', 'a2', 'a3', 'a4', 'logits', 'value'):
+        t[k].fill_(float('nan'))
+    ws = torch.full((int(lib.acmi_forward_ws_floats(B)),), float('nan'), device=cuda)
+    acts.ws, acts.ws_floats = ws.data_ptr(), ws.numel()
+    net = _net(params, A, C3)
+    _lib.call('acmi_forward', ctypes.byref(net), _lib.ptr(obs), 84 * 84 * 4, B, ctypes.byref(acts), 1,
+              _lib.stream_handle())
+    torch.cuda.synchronize()
+    rows = list(range(8)) + list(range(B - 8, B))
+    ref = dict(zip(['a1', 'a2', 'a3', 'a4', 'logits', 'value'], torch_forward(params, obs[rows].cpu(), A, C3)))
+    errs = {}
+    for name in ('a4', 'logits', 'value'):
+        r = ref[name]
+        got = t[name][rows].cpu().double().reshape(r.shape)
+        errs[name] = (got - r).abs().max().item() / max(1e-6, r.abs().max().item())
+    return errs
+
+
+@pytest.mark.parametrize('B,nz,gemm', [(2001, 2, 'x3'), (1401, 3, 'x3'), (1001, 4, 'x3'), (801, 5, 'x3'),
+                                       (701, 6, 'x3'), (601, 7, 'x3'), (101, 13, 'f32')])
+def test_forward_split_counts_match_float64(lib, cuda, B, nz, gemm):
+    """acmi_forward with its workspace at the fc4 split counts no other test or the
+    benchmark reaches: 2 .. 7 slabs (x3 mode) and 13 (f32 mode below 128 images, K =
+    1568 in chunks of 4 k32-steps), each through its own heads_kernel<NZ>.  The batch
+    sizes are odd, so the last heads block is partly empty; activations and workspace
+    start as NaN, so a slab or a row left out shows.  The bound is
+    test_forward_matches_torch's."""
+    mode = _lib.GEMM_X3 if gemm == 'x3' else _lib.GEMM_F32
+    errs = _with_mode(lib, mode, _forward_split_count_errors, lib, cuda, B, nz, gemm)
+    print(B, nz, gemm, errs)
+    for name, rel in errs.items():
+        assert rel < 1e-5, (name, rel)  # (NaN fails too)
+
+
 def _backward_errors(lib, cuda, B=6, seed=3):
     """max relative errors of acmi_backward's parameter gradients and A factors
     against float64 autograd / patch products"""
