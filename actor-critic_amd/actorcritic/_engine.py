@@ -172,6 +172,32 @@ class UpdateState(object):
         return self._side
 
 
+def host_action_masks(masks, num_actions):
+    """Host-side validation of per-env legal-action words (bit a set = action a is
+    legal): a non-empty 1-d integer array, every set non-empty, no bit at or above
+    ``num_actions``, ``num_actions`` <= 32.  -> the words as a uint32 ndarray."""
+    if num_actions > _lib.MASK_MAX_ACTIONS:
+        raise ValueError('legal-action masks take at most {} actions, the model has {}'
+                         .format(_lib.MASK_MAX_ACTIONS, num_actions))
+    w = np.asarray(masks)
+    if w.ndim != 1 or w.size == 0 or w.dtype.kind not in 'iu':
+        raise ValueError('action masks must be a non-empty 1-d integer array, one word per env')
+    w = w.astype(np.int64) & 0xFFFFFFFF
+    for n, word in enumerate(w):
+        if word == 0:
+            raise ValueError('env {}: empty legal-action set'.format(n))
+        if word >> num_actions:
+            raise ValueError('env {}: mask {:#x} has bits at or above num_actions={}'
+                             .format(n, int(word), num_actions))
+    return w.astype(np.uint32)
+
+
+def check_mask_count(num_masks, num_envs):
+    """ValueError unless a forward of ``num_envs`` envs has one mask word per env."""
+    if num_masks != num_envs:
+        raise ValueError('action masks are set for {} envs, the forward has {}'.format(num_masks, num_envs))
+
+
 class NetEngine(object):
     """Parameters + kernels of one AtariModel on one device."""
 
@@ -202,7 +228,15 @@ class NetEngine(object):
         self._acts = {}
         self._updates = {}
         self._rollout_cache = None
-        self._bad_rows = torch.zeros(1, dtype=torch.int32, device=self.device)
+        # [rows with non-finite logits (or an empty legal set) | bad rows of the masked loss
+        # kernels]: one buffer, so one read serves both counters (check_bad_rows)
+        self._bad_counts = torch.zeros(2, dtype=torch.int32, device=self.device)
+        self._bad_rows = self._bad_counts[:1]
+        self._mask_bad_rows = self._bad_counts[1:]
+        # legal-action masks (set_action_masks): one word per env of this rank, kept as
+        # the uint32 bits in an int32 tensor, and their per-row expansions by steps T
+        self.masks = None
+        self._mask_rows = {}
         self._prep, self._prep_version = None, None
         self.sample_counter = 0
         self._comm = None  # comm_timing: [(start event, end event, bytes)] per update
@@ -239,6 +273,37 @@ class NetEngine(object):
             return c[4]
         return None
 
+    # -- legal-action masks -------------------------------------------------------
+    def set_action_masks(self, masks):
+        """One legal-action word per env of this rank (bit a set = action a is legal),
+        or None to clear them.  A host array / list is validated here (non-empty sets,
+        no bits at or above A); a device tensor (uint32 or int32 bits) is taken as it is."""
+        self._mask_rows = {}
+        if masks is None:
+            self.masks = None
+            return
+        if self.A > _lib.MASK_MAX_ACTIONS:
+            raise ValueError('legal-action masks take at most {} actions, the model has {}'
+                             .format(_lib.MASK_MAX_ACTIONS, self.A))
+        if isinstance(masks, torch.Tensor) and masks.is_cuda:
+            if masks.dtype not in (torch.uint32, torch.int32) or masks.dim() != 1 or masks.numel() == 0:
+                raise ValueError('device action masks must be a non-empty 1-d uint32 (or int32) tensor')
+            t = masks.contiguous().view(torch.int32).to(self.device)
+        else:
+            w = masks.cpu().numpy() if isinstance(masks, torch.Tensor) else masks
+            t = torch.from_numpy(host_action_masks(w, self.A).view(np.int32)).to(self.device)
+        self.masks = t
+
+    def row_masks(self, batch, steps=1):
+        """The per-row words of an env-major [batch][steps] block (cached per steps);
+        ValueError when ``batch`` is not the number of envs the masks were set for."""
+        check_mask_count(self.masks.numel(), batch)
+        if steps == 1:
+            return self.masks
+        if steps not in self._mask_rows:
+            self._mask_rows[steps] = self.masks.repeat_interleave(steps).contiguous()
+        return self._mask_rows[steps]
+
     def backward(self, fwd, st, with_stats):
         net = self.net()
         _lib.call('acmi_backward', ctypes.byref(net), ctypes.c_void_p(fwd.obs.data_ptr()), OBS_BYTES, fwd.M,
@@ -264,6 +329,12 @@ class NetEngine(object):
         """side: run on UpdateState.side()'s stream and workspace (see there)."""
         net = self.net()
         bwd, ws = (side.bwd, side.ws) if side is not None else (st.bwd, st.bwd_ws)
+        if self.masks is not None:  # y ~ Cat over each row's legal set
+            _lib.call('acmi_kfac_output_stats_masked', ctypes.byref(net), fwd.M, ctypes.byref(fwd.acts.struct),
+                      ctypes.byref(bwd), seed, self.rank * fwd.M, counter,
+                      _lib.ptr(self.row_masks(fwd.batch, fwd.steps)), _lib.ptr(st.gstat), _lib.ptr(ws), ws.numel(),
+                      self.stream())
+            return
         _lib.call('acmi_kfac_output_stats', ctypes.byref(net), fwd.M, ctypes.byref(fwd.acts.struct),
                   ctypes.byref(bwd), seed, self.rank * fwd.M, counter, _lib.ptr(st.gstat), _lib.ptr(ws),
                   ws.numel(), self.stream())
@@ -292,7 +363,8 @@ class NetEngine(object):
         as it is enqueued and returns its handle (allreduce_end completes it).  With
         ``concurrent_stats`` the G chain runs on a side stream next to the backward."""
         conc = self.concurrent_stats if self.concurrent_stats is not None else fwd.M <= self.CONCURRENT_STATS_ROWS
-        if with_stats and not conc and self.stacked_dx:
+        # (acmi_backward_stacked has no masked form: with masks the two calls)
+        if with_stats and not conc and self.stacked_dx and self.masks is None:
             sd = st.side(self)  # (its d1..d4 and workspace; the work stays on this stream)
             self.backward_stacked(fwd, st, sd, seed, counter)
             pending = self.allreduce_begin(st, True)
@@ -453,6 +525,13 @@ class NetEngine(object):
         return acts, obs
 
     def sample(self, logits, B, out, mode=False, seed=0, stream_id=0, uniforms=None, ld=None):
+        if self.masks is not None:
+            _lib.call('acmi_sample_actions_masked', ctypes.c_void_p(logits.data_ptr()), ld or self.A, B, self.A,
+                      seed, stream_id, None, self.sample_counter, 0, _lib.ptr(uniforms), 1 if mode else 0,
+                      _lib.ptr(self.row_masks(B)), ctypes.c_void_p(out.data_ptr()),
+                      ctypes.c_void_p(self._bad_rows.data_ptr()), self.stream())
+            self.sample_counter += 1
+            return
         _lib.call('acmi_sample_actions', ctypes.c_void_p(logits.data_ptr()), ld or self.A, B, self.A, seed,
                   stream_id, self.sample_counter, _lib.ptr(uniforms), 1 if mode else 0,
                   ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(self._bad_rows.data_ptr()), self.stream())
@@ -460,7 +539,11 @@ class NetEngine(object):
 
     def check_bad_rows(self):
         """Raises like the reference's out-of-range label error if any logits were NaN."""
-        bad = int(self._bad_rows.item())
+        bad, mask_bad = self._bad_counts.tolist()
+        if mask_bad:
+            self._bad_counts.zero_()
+            raise ValueError('{} rows of a masked loss had an empty legal-action set or a taken action outside '
+                             'it (were the actions drawn under other masks?)'.format(mask_bad))
         if bad:
             self._bad_rows.zero_()
             raise FloatingPointError('{} policy rows had non-finite logits (reference: InvalidArgumentError '

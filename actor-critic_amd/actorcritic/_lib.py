@@ -89,6 +89,19 @@ _SIGS = {
     'acmi_rollout_step': (c_int, [ctypes.POINTER(Net), c_vp, c_i64, c_int, ctypes.POINTER(Acts), c_i64,
                                   ctypes.POINTER(RolloutIO), c_vp]),
     'acmi_categorical': (c_int, [c_vp, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp]),
+    # legal-action masks: the unmasked argument lists + legal (device uint32 per row) (+ bad_rows)
+    'acmi_sample_actions_masked': (c_int, [c_vp, c_int, c_int, c_int, c_u32, c_u32, c_vp, c_u32, c_int, c_vp,
+                                           c_int, c_vp, c_vp, c_vp, c_vp]),
+    'acmi_categorical_masked': (c_int, [c_vp, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    'acmi_a2c_loss_masked': (c_int, [c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_float, c_float, c_float,
+                                     c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    'acmi_ppo_loss_masked': (c_int, [c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_float,
+                                     c_float, c_float, c_float, c_float, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                     c_vp]),
+    'acmi_kfac_output_stats_masked': (c_int, [ctypes.POINTER(Net), c_int, ctypes.POINTER(Acts), ctypes.POINTER(Bwd),
+                                              c_u32, c_u32, c_u32, c_vp, c_vp, c_vp, c_i64, c_vp]),
+    'acmi_rollout_step_masked': (c_int, [ctypes.POINTER(Net), c_vp, c_i64, c_int, ctypes.POINTER(Acts), c_i64,
+                                         ctypes.POINTER(RolloutIO), c_vp, c_vp]),
     'acmi_returns': (c_int, [c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp]),
     'acmi_gae': (c_int, [c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_float, c_float, c_vp, c_vp, c_vp]),
     'acmi_adv_moments_ws_doubles': (c_i64, [c_i64]),
@@ -161,6 +174,9 @@ ERR_ARG = -1  # acmi_status_t ACMI_ERR_ARG
 # the A + 1 heads of one env in 32 floats of LDS (acmi.h); every other entry point
 # takes the whole 1..64 (agents.py steps wider action sets unfused)
 ROLLOUT_STEP_MAX_ACTIONS = 31
+
+# the *_masked entry points: a legal-action word holds 32 actions
+MASK_MAX_ACTIONS = 32
 
 PROF_CONV1_WGRAD = 1
 PROF_CONV2_WGRAD = 2

@@ -80,7 +80,7 @@ class _RolloutBuffers(object):
         self.terminals = torch.zeros((N, T), dtype=torch.uint8, device=dev)
         self.episode_rewards = torch.zeros((N, T), dtype=torch.float32, device=dev)
         self.acts = engine.activations(N * T, 'rollout')
-        self.bad_host = torch.zeros(1, dtype=torch.int32, pin_memory=True)
+        self.bad_host = torch.zeros(2, dtype=torch.int32, pin_memory=True)  # (engine._bad_counts)
         self.bad_event = None
         # two-chain rollout: env halves on the current stream and a side stream,
         # each with its own forward workspace (fc4 split-K slabs)
@@ -117,13 +117,25 @@ class _HostRolloutBuffers(object):
 class MultiEnvAgent(Agent):
     """Multiple envs (MultiEnv), multiple steps (agents.py:134-228)."""
 
-    def __init__(self, multi_env, model, num_steps, copy_batches=False):
+    def __init__(self, multi_env, model, num_steps, copy_batches=False, mask_actions=False):
+        """mask_actions: take the batched env's ``legal_action_masks`` (one word per env)
+        and set them on the model (AtariModel.set_action_masks): every action is then
+        drawn from its env's legal set, and the losses / K-FAC statistics of that model
+        run over it.  Off by default.  (Every rollout form follows the masks the model
+        holds, however they were set.)"""
         self._env = multi_env
         self._model = model
         self._num_steps = num_steps
         self._observations = None
         self._bufs = None
         self._copy = bool(copy_batches)
+        self._mask_actions = bool(mask_actions)
+        if self._mask_actions:
+            masks = getattr(getattr(multi_env, 'batched', None), 'legal_action_masks', None)
+            if masks is None:
+                raise ValueError('mask_actions=True needs a batched env with legal_action_masks '
+                                 '(SyntheticAtariEnvs(games=...) or HostAtariEnvs(legal_actions=...))')
+            model.set_action_masks(masks)
 
     def _fast(self):
         return getattr(self._env, 'batched', None) is not None and hasattr(self._model, 'engine')
@@ -201,7 +213,8 @@ class MultiEnvAgent(Agent):
         # arithmetic modes / step fusion that chose the captured kernels
         lib = eng.lib
         key = (eng.params.data_ptr(), id(env), seed, eng.rank, int(lib.acmi_get_gemm_mode()),
-               int(lib.acmi_get_forward_mode()), bool(rb.fuse_steps))
+               int(lib.acmi_get_forward_mode()), bool(rb.fuse_steps),
+               None if eng.masks is None else eng.masks.data_ptr())
         if rb.graph is None or rb.graph_key != key:
             if not rb.warm:  # first rollout eager: loads the code objects, sizes workspaces
                 rb.warm = True
@@ -230,12 +243,13 @@ class MultiEnvAgent(Agent):
             t_wait = time.perf_counter()
             rb.bad_event.synchronize()
             self.last_sync_wait = time.perf_counter() - t_wait  # (bench.py's host-time split)
-            if int(rb.bad_host[0]) > 0:
+            if int(rb.bad_host[0]) > 0 or int(rb.bad_host[1]) > 0:
                 eng.check_bad_rows()
         if self._observations is None:
             env.reset_into(rb.next_obs.data_ptr())
         stream = eng.stream()
         A = eng.A
+        legal = _mask_rows(eng, N)
         obs0 = rb.obs.data_ptr()
         rew0, term0, ep0 = rb.rewards.data_ptr(), rb.terminals.data_ptr(), rb.episode_rewards.data_ptr()
         seed = (self._model._random_seed or 0) & 0xFFFFFFFF
@@ -249,9 +263,15 @@ class MultiEnvAgent(Agent):
                 src = obs0 + t * OBS_BYTES
                 eng.forward(src, N, rb.acts.view(t, T), want_value=True, img_stride=T * OBS_BYTES, act_stride=T)
                 act_t = rb.actions_tn[t]
-                _lib.call('acmi_sample_actions_at', _lib.c_vp(rb.acts.logits.data_ptr() + 4 * t * A), T * A, N,
-                          A, seed, 0, eng.sample_counter, eng.rank * N, None, 0, _lib.c_vp(act_t.data_ptr()),
-                          _lib.c_vp(eng._bad_rows.data_ptr()), stream)
+                if legal is not None:
+                    _lib.call('acmi_sample_actions_masked', _lib.c_vp(rb.acts.logits.data_ptr() + 4 * t * A), T * A,
+                              N, A, seed, 0, None, eng.sample_counter & 0xFFFFFFFF, eng.rank * N, None, 0,
+                              _lib.c_vp(legal), _lib.c_vp(act_t.data_ptr()), _lib.c_vp(eng._bad_rows.data_ptr()),
+                              stream)
+                else:
+                    _lib.call('acmi_sample_actions_at', _lib.c_vp(rb.acts.logits.data_ptr() + 4 * t * A), T * A, N,
+                              A, seed, 0, eng.sample_counter, eng.rank * N, None, 0, _lib.c_vp(act_t.data_ptr()),
+                              _lib.c_vp(eng._bad_rows.data_ptr()), stream)
                 eng.sample_counter += 1
                 if t + 1 < T:
                     dst, dstride = obs0 + (t + 1) * OBS_BYTES, T * OBS_BYTES
@@ -260,7 +280,7 @@ class MultiEnvAgent(Agent):
                 env.step_into(act_t.data_ptr(), src, T * OBS_BYTES, dst, dstride, rew0 + 4 * t, term0 + t,
                               ep0 + 4 * t, T)
             rb.actions.copy_(rb.actions_tn.t())
-        rb.bad_host.copy_(eng._bad_rows, non_blocking=True)
+        rb.bad_host.copy_(eng._bad_counts, non_blocking=True)
         rb.bad_event = torch.cuda.Event()
         rb.bad_event.record()
         return self._batch(eng, rb, N, T)
@@ -279,6 +299,7 @@ class MultiEnvAgent(Agent):
         if self._observations is None:
             env.reset_into(rb.next_obs.data_ptr())
         A = eng.A
+        legal = _mask_rows(eng, N)
         stream = eng.stream()
         obs0 = rb.obs.data_ptr()
         seed = (self._model._random_seed or 0) & 0xFFFFFFFF
@@ -289,9 +310,14 @@ class MultiEnvAgent(Agent):
             src = obs0 + t * OBS_BYTES
             eng.forward(src, N, rb.acts.view(t, T), want_value=True, img_stride=T * OBS_BYTES, act_stride=T)
             row = hb.act_bad[t]  # [actions of step t (N) | rows with non-finite logits (1)]
-            _lib.call('acmi_sample_actions_at', _lib.c_vp(rb.acts.logits.data_ptr() + 4 * t * A), T * A, N, A,
-                      seed, 0, eng.sample_counter & 0xFFFFFFFF, eng.rank * N, None, 0, _lib.c_vp(row.data_ptr()),
-                      _lib.c_vp(row.data_ptr() + 4 * N), stream)
+            if legal is not None:
+                _lib.call('acmi_sample_actions_masked', _lib.c_vp(rb.acts.logits.data_ptr() + 4 * t * A), T * A, N,
+                          A, seed, 0, None, eng.sample_counter & 0xFFFFFFFF, eng.rank * N, None, 0,
+                          _lib.c_vp(legal), _lib.c_vp(row.data_ptr()), _lib.c_vp(row.data_ptr() + 4 * N), stream)
+            else:
+                _lib.call('acmi_sample_actions_at', _lib.c_vp(rb.acts.logits.data_ptr() + 4 * t * A), T * A, N, A,
+                          seed, 0, eng.sample_counter & 0xFFFFFFFF, eng.rank * N, None, 0,
+                          _lib.c_vp(row.data_ptr()), _lib.c_vp(row.data_ptr() + 4 * N), stream)
             eng.sample_counter += 1
             hb.act_bad_host.copy_(row, non_blocking=True)
             hb.event.record()
@@ -327,6 +353,14 @@ class MultiEnvAgent(Agent):
         return out[:5] + (EpisodeInfoBatch(out[5]),)
 
 
+def _mask_rows(eng, N):
+    """Device address of the engine's per-env legal-action words (None: no masks);
+    ValueError unless there is one word per env of the rollout."""
+    if eng.masks is None:
+        return None
+    return eng.row_masks(N).data_ptr()
+
+
 def _half_step(eng, env, rb, h, N2, T, A, t, seed, dev_ctr=False, fuse=False):
     """Rollout step t of env half h (envs h*N2 .. h*N2+N2-1) on the current stream.
     dev_ctr: the sampler's RNG counter is rb.ctr_dev + t (graph capture) instead of
@@ -343,6 +377,9 @@ def _half_step(eng, env, rb, h, N2, T, A, t, seed, dev_ctr=False, fuse=False):
     # the sampler's RNG is keyed by the global env row (stream 0): env shards over
     # ranks draw exactly what one process stepping all envs would
     row0 = eng.rank * rb.N + n0
+    legal = _mask_rows(eng, rb.N)
+    if legal is not None:
+        legal += 4 * n0  # (the env half's words)
     if dev_ctr:
         ctr_dev, ctr = _lib.c_vp(rb.ctr_dev.data_ptr()), t
     else:
@@ -366,10 +403,20 @@ def _half_step(eng, env, rb, h, N2, T, A, t, seed, dev_ctr=False, fuse=False):
                             env.env_offset + n0, env.seed, dst, dstride, rew, term, ep, T,
                             1 if fuse and t > 0 else 0, ctypes.addressof(nxt) if nxt is not None else None, T,
                             src if t == 0 else None)
-        _lib.call('acmi_rollout_step', ctypes.byref(eng.net()), ctypes.c_void_p(src_t), sstride, N2,
-                  ctypes.byref(acts), T, ctypes.byref(io), eng.stream())
+        if legal is not None:
+            _lib.call('acmi_rollout_step_masked', ctypes.byref(eng.net()), ctypes.c_void_p(src_t), sstride, N2,
+                      ctypes.byref(acts), T, ctypes.byref(io), _lib.c_vp(legal), eng.stream())
+        else:
+            _lib.call('acmi_rollout_step', ctypes.byref(eng.net()), ctypes.c_void_p(src_t), sstride, N2,
+                      ctypes.byref(acts), T, ctypes.byref(io), eng.stream())
         return
     eng.forward(src, N2, acts, want_value=True, img_stride=T * OBS_BYTES, act_stride=T)
+    if legal is not None:
+        _lib.call('acmi_sample_actions_masked', _lib.c_vp(rb.acts.logits.data_ptr() + 4 * row * A), T * A, N2, A,
+                  seed, 0, ctr_dev, ctr, row0, None, 0, _lib.c_vp(legal), _lib.c_vp(act_t),
+                  _lib.c_vp(eng._bad_rows.data_ptr()), eng.stream())
+        env.step_range_into(n0, N2, act_t, src, T * OBS_BYTES, dst, dstride, rew, term, ep, T)
+        return
     _lib.call('acmi_sample_actions_dev', _lib.c_vp(rb.acts.logits.data_ptr() + 4 * row * A), T * A, N2, A,
               seed, 0, ctr_dev, ctr, row0, None, 0, _lib.c_vp(act_t),
               _lib.c_vp(eng._bad_rows.data_ptr()), eng.stream())

@@ -9,7 +9,7 @@ libacmi (acmi_forward); parameters live in one flat fp32 device vector
 import torch
 
 from actorcritic import spaces
-from actorcritic._engine import NetEngine, _as_obs
+from actorcritic._engine import NetEngine, _as_obs, check_mask_count
 from actorcritic import _lib
 from actorcritic.baselines import StateValueFunction
 from actorcritic.model import ActorCriticModel
@@ -42,8 +42,19 @@ class ForwardOut(object):
     def value(self):
         return self.flat_value.reshape(self.batch, self.steps)
 
+    def row_masks(self):
+        """The rows' legal-action words (None without masks on the engine)."""
+        if self.engine.masks is None:
+            return None
+        return self.engine.row_masks(self.batch, self.steps)
+
     def entropy(self):
         out = torch.empty(self.M, dtype=torch.float32, device=self.engine.device)
+        legal = self.row_masks()
+        if legal is not None:
+            _lib.call('acmi_categorical_masked', _lib.ptr(self.flat_logits), self.engine.A, self.M, self.engine.A,
+                      None, _lib.ptr(legal), _lib.ptr(out), None, self.engine.stream())
+            return out.reshape(self.batch, self.steps)
         _lib.call('acmi_categorical', _lib.ptr(self.flat_logits), self.engine.A, self.M, self.engine.A, None,
                   _lib.ptr(out), None, self.engine.stream())
         return out.reshape(self.batch, self.steps)
@@ -53,6 +64,11 @@ class ForwardOut(object):
         if a.numel() != self.M:
             raise ValueError('actions shape does not match the observations')
         out = torch.empty(self.M, dtype=torch.float32, device=self.engine.device)
+        legal = self.row_masks()
+        if legal is not None:
+            _lib.call('acmi_categorical_masked', _lib.ptr(self.flat_logits), self.engine.A, self.M, self.engine.A,
+                      _lib.ptr(a), _lib.ptr(legal), None, _lib.ptr(out), self.engine.stream())
+            return out.reshape(self.batch, self.steps)
         _lib.call('acmi_categorical', _lib.ptr(self.flat_logits), self.engine.A, self.M, self.engine.A, _lib.ptr(a),
                   None, _lib.ptr(out), self.engine.stream())
         return out.reshape(self.batch, self.steps)
@@ -92,6 +108,8 @@ class _TowerForward(Node):
                 shape = np.shape(x)
             batch, steps = int(shape[0]), int(shape[1])
         M = batch * steps
+        if eng.masks is not None:
+            check_mask_count(eng.masks.numel(), batch)
         acts = eng.activations(M, 'boot' if self.bootstrap else 'feed')
         eng.forward(obs.data_ptr(), M, acts.struct, want_value=True)
         return ForwardOut(eng, acts, batch, steps, obs)
@@ -163,6 +181,22 @@ class AtariModel(ActorCriticModel):
     def params(self):
         """The flat fp32 parameter vector (device tensor)."""
         return self._engine.params
+
+    def set_action_masks(self, masks):
+        """Legal-action masks (invalid-action masking), opt-in: one uint32 word per env
+        of this rank, bit a set = action a is legal (wrappers.action_mask_bits), as a
+        host array / list (validated: non-empty sets, no bits at or above the number
+        of actions) or a device tensor; None clears them.  Needs at most 32 actions.
+        With masks set the policy's sample / mode / entropy / log_prob, the A2C / PPO
+        losses and K-FAC's sampled head gradients run over each env's legal set
+        (acmi.h, the *_masked entry points); a fed batch must then have one env per word."""
+        self._engine.set_action_masks(masks)
+
+    @property
+    def action_masks(self):
+        """The legal-action words on the device (uint32), or None."""
+        m = self._engine.masks
+        return None if m is None else m.view(torch.uint32)
 
     def named_params(self):
         """{'conv1/weights': tensor view, ...} in the reference's variable naming."""

@@ -56,6 +56,35 @@ def game_index(name):
     raise ValueError('unknown Atari-57 game {!r}'.format(name))
 
 
+def action_mask_bits(legal_actions, num_actions):
+    """The legal-action word of one env (host-only): bit a set = action a is legal
+    (the ``legal`` argument of libacmi's *_masked entry points, acmi.h).  Raises
+    ValueError for an empty set, an index outside [0, num_actions) or
+    num_actions > 32 (a word holds 32 actions)."""
+    num_actions = int(num_actions)
+    if not 1 <= num_actions <= 32:
+        raise ValueError('legal-action masks take 1 .. 32 actions, got num_actions={}'.format(num_actions))
+    bits = 0
+    for a in legal_actions:
+        if int(a) != a or not 0 <= int(a) < num_actions:
+            raise ValueError('legal action {!r} outside [0, {})'.format(a, num_actions))
+        bits |= 1 << int(a)
+    if bits == 0:
+        raise ValueError('an env needs at least one legal action')
+    return bits
+
+
+def game_action_masks(games, num_actions=18):
+    """Host-side: the legal-action words of Atari-57 games (names / indices) under a
+    ``num_actions``-wide head -- game g's minimal action set is the prefix
+    0 .. ATARI57_ACTIONS[g]-1, the stepper's n_legal (csrc/stepper.hpp kGameActions)."""
+    return [action_mask_bits(range(ATARI57_ACTIONS[game_index(g)]), num_actions) for g in games]
+
+
+def _mask_tensor(words, device):
+    return torch.from_numpy(np.asarray(words, dtype=np.uint32)).to(device)
+
+
 def num_actions_for(env_id):
     for k, v in ATARI_NUM_ACTIONS.items():
         if env_id.startswith(k):
@@ -181,6 +210,7 @@ class SyntheticAtariEnvs(object):
         self._episode, self._step, self._length = z(torch.int32), z(torch.int32), z(torch.int32)
         self._total, self._done = z(torch.float32), z(torch.uint8)
         self.games = None
+        self.legal_action_masks = None  # (no games: every action distinct, nothing to mask)
         if games is not None:
             if isinstance(games, str) and games == 'atari57':
                 idx = [(self.env_offset + n) % len(ATARI57) for n in range(N)]
@@ -193,6 +223,9 @@ class SyntheticAtariEnvs(object):
             if max(ATARI57_ACTIONS[i] for i in idx) > num_actions:
                 raise ValueError('num_actions={} is smaller than a game\'s action set'.format(num_actions))
             self.games = torch.tensor(idx, dtype=torch.uint8, device=self.device)
+            if num_actions <= 32:
+                # one legal-action word per env (uint32, device): MultiEnvAgent(mask_actions=True)
+                self.legal_action_masks = _mask_tensor(game_action_masks(idx, num_actions), self.device)
         self.state = _lib.EnvState(self._episode.data_ptr(), self._step.data_ptr(), self._length.data_ptr(),
                                    self._total.data_ptr(), self._done.data_ptr(), self._game_ptr(0))
         self._obs = torch.zeros((N, 84, 84, 4), dtype=torch.uint8, device=self.device)
@@ -379,13 +412,23 @@ class HostAtariEnvs(object):
 
     host_stepped = True
 
-    def __init__(self, envs, height=RAW_HEIGHT, width=RAW_WIDTH, device=None):
+    def __init__(self, envs, height=RAW_HEIGHT, width=RAW_WIDTH, device=None, legal_actions=None):
+        """legal_actions: None, or per env the list of its legal action indices (any
+        subset of the action space, e.g. a game's minimal set inside the full 18):
+        ``legal_action_masks`` then holds one uint32 word per env on the device."""
         import concurrent.futures
         self.device = _device_of(device)
         self._envs = list(envs)
         self.num_envs = N = len(self._envs)
         if N == 0:
             raise ValueError('HostAtariEnvs needs at least one env')
+        self.legal_action_masks = None
+        if legal_actions is not None:
+            legal_actions = list(legal_actions)
+            if len(legal_actions) != N:
+                raise ValueError('legal_actions: {} entries for {} envs'.format(len(legal_actions), N))
+            words = [action_mask_bits(la, self._envs[0].action_space.n) for la in legal_actions]
+            self.legal_action_masks = _mask_tensor(words, self.device)
         self.height, self.width = int(height), int(width)
         self.observation_space = spaces.Box(low=0, high=255, shape=(84, 84, 4), dtype=np.uint8)
         self.action_space = self._envs[0].action_space

@@ -7,6 +7,7 @@ Atari stepper in place of ALE subprocesses.
 """
 
 import os
+import sys
 
 import numpy as np
 
@@ -22,24 +23,27 @@ from actorcritic.session import Session, get_or_create_global_step, no_op
 
 
 def train_a2c_acktr(acktr, env_id, num_envs, num_steps, checkpoint_path, model_name, summary_path=None,
-                    max_updates=None, seed=0, log_every=10, env_fns=None):
+                    max_updates=None, seed=0, log_every=10, env_fns=None, mask_actions=False):
     """Trains an Atari model with A2C (RMSProp, conv3 64) or ACKTR (K-FAC, conv3 32).
 
     ``num_envs`` is per GPU; with WORLD_SIZE > 1 (torchrun) every rank steps its own shard.
     ``env_fns``: None (the synthetic batched stepper) or one function per env of this rank
     that makes a host env with raw RGB frames (create_host_environments); ``num_envs`` is
     then their number.
+    ``mask_actions`` (``--mask-actions``): invalid-action masking -- the synthetic game under the
+    full 18-action head with its minimal action set as the legal set (host envs: their
+    ``legal_action_masks``); actions, losses and K-FAC statistics then run over the legal set.
     """
     parallel.init_from_env()
     if env_fns is not None:
         multi_env = create_host_environments(env_fns)
         num_envs = multi_env.num_envs
     else:
-        multi_env = MultiEnv(create_environments(env_id, num_envs, seed=seed))
+        multi_env = MultiEnv(create_environments(env_id, num_envs, seed=seed, full_action_set=mask_actions))
 
     conv3_num_filters = 32 if acktr else 64
     model = AtariModel(multi_env.observation_space, multi_env.action_space, conv3_num_filters, random_seed=seed)
-    agent = MultiEnvAgent(multi_env, model, num_steps)
+    agent = MultiEnvAgent(multi_env, model, num_steps, mask_actions=mask_actions)
     objective = A2CObjective(model, discount_factor=0.99, entropy_regularization_strength=0.01)
 
     global_step = get_or_create_global_step()
@@ -96,8 +100,13 @@ def train_a2c_acktr(acktr, env_id, num_envs, num_steps, checkpoint_path, model_n
     return model, optimizer
 
 
-def create_environments(env_id, num_envs, seed=0):
-    """The batched synthetic Atari stepper for this rank's env shard."""
+def create_environments(env_id, num_envs, seed=0, full_action_set=False):
+    """The batched synthetic Atari stepper for this rank's env shard.  ``full_action_set``:
+    the game (an Atari-57 name) under the full 18-action set, its minimal action set in
+    ``legal_action_masks`` (MultiEnvAgent(mask_actions=True))."""
+    if full_action_set:
+        return wrappers.SyntheticAtariEnvs(num_envs, num_actions=18, seed=seed, games=[env_id] * num_envs,
+                                           env_offset=parallel.rank() * num_envs)
     return wrappers.SyntheticAtariEnvs(num_envs, num_actions=wrappers.num_actions_for(env_id), seed=seed,
                                        env_offset=parallel.rank() * num_envs)
 
@@ -155,4 +164,5 @@ if __name__ == '__main__':
     summary_path = results_path + '/summaries/' + env_id
     os.makedirs(checkpoint_path, exist_ok=True)
     os.makedirs(summary_path, exist_ok=True)
-    train_a2c_acktr(acktr, env_id, num_envs, num_steps, checkpoint_path, 'Atari-' + env_id, summary_path)
+    train_a2c_acktr(acktr, env_id, num_envs, num_steps, checkpoint_path, 'Atari-' + env_id, summary_path,
+                    mask_actions='--mask-actions' in sys.argv[1:])

@@ -11,6 +11,7 @@ all env-steps of the batch per epoch (objectives.PPOOptimizeOp).
 """
 
 import os
+import sys
 
 import numpy as np
 
@@ -28,7 +29,7 @@ from actorcritic.session import Session, get_or_create_global_step, no_op
 
 def train_ppo(env_id, num_envs, num_steps, checkpoint_path, model_name, summary_path=None, max_updates=None, seed=0,
               log_every=10, num_epochs=4, num_minibatches=4, clip_range=0.1, value_clip_range=None,
-              minibatch='envs', env_fns=None):
+              minibatch='envs', env_fns=None, mask_actions=False):
     """Trains an Atari model (conv3 64) with PPO.
 
     ``num_envs`` is per GPU; with WORLD_SIZE > 1 (torchrun) every rank steps its own shard.
@@ -39,16 +40,17 @@ def train_ppo(env_id, num_envs, num_steps, checkpoint_path, model_name, summary_
     ``env_fns``: None (the synthetic batched stepper) or one function per env of this rank that
     makes a host env with raw RGB frames (a2c_acktr.create_host_environments); ``num_envs`` is
     then their number.
+    ``mask_actions`` (``--mask-actions``): invalid-action masking, as in a2c_acktr.train_a2c_acktr.
     """
     parallel.init_from_env()
     if env_fns is not None:
         multi_env = create_host_environments(env_fns)
         num_envs = multi_env.num_envs
     else:
-        multi_env = MultiEnv(create_environments(env_id, num_envs, seed=seed))
+        multi_env = MultiEnv(create_environments(env_id, num_envs, seed=seed, full_action_set=mask_actions))
 
     model = AtariModel(multi_env.observation_space, multi_env.action_space, 64, random_seed=seed)
-    agent = MultiEnvAgent(multi_env, model, num_steps)
+    agent = MultiEnvAgent(multi_env, model, num_steps, mask_actions=mask_actions)
     objective = PPOObjective(model, discount_factor=0.99, entropy_regularization_strength=0.01,
                              clip_range=clip_range, value_clip_range=value_clip_range, gae_lambda=0.95,
                              normalize_advantages=True)
@@ -123,4 +125,5 @@ if __name__ == '__main__':
     summary_path = results_path + '/summaries-ppo/' + env_id
     os.makedirs(checkpoint_path, exist_ok=True)
     os.makedirs(summary_path, exist_ok=True)
-    train_ppo(env_id, num_envs, num_steps, checkpoint_path, 'Atari-' + env_id, summary_path)
+    train_ppo(env_id, num_envs, num_steps, checkpoint_path, 'Atari-' + env_id, summary_path,
+              mask_actions='--mask-actions' in sys.argv[1:])

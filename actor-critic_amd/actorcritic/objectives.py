@@ -158,6 +158,14 @@ class _Loss(Node):
         # the kernel scales the loss scalars by 1/world like dhead; they hold the
         # global means once the update's all-reduce has summed them (loss_reduced)
         st.loss_reduced = eng.world_size == 1
+        st.fwd = fwd
+        legal = fwd.row_masks()
+        if legal is not None:  # over each row's legal set; bad rows count in the engine's counter
+            _lib.call('acmi_a2c_loss_masked', _lib.ptr(fwd.flat_logits), eng.A, _lib.ptr(fwd.flat_value),
+                      _lib.ptr(actions), _lib.ptr(st.targets), _lib.ptr(st.adv), M, eng.A, float(obj._beta),
+                      float(obj._vcoef), 1.0 / eng.world_size, _lib.ptr(st.dhead), eng.ldh, _lib.ptr(st.loss_ws),
+                      _lib.ptr(st.loss), _lib.ptr(legal), _lib.ptr(eng._mask_bad_rows), eng.stream())
+            return st.loss
         _lib.call('acmi_a2c_loss', _lib.ptr(fwd.flat_logits), eng.A, _lib.ptr(fwd.flat_value), _lib.ptr(actions),
                   _lib.ptr(st.targets), _lib.ptr(st.adv), M, eng.A, float(obj._beta), float(obj._vcoef),
                   1.0 / eng.world_size, _lib.ptr(st.dhead), eng.ldh, _lib.ptr(st.loss_ws), _lib.ptr(st.loss),
@@ -273,14 +281,17 @@ def ppo_row_order(shuffle_seed, step, num_epochs, M):
 class _PPORun(object):
     """What one session.run shares between the PPO nodes."""
 
-    def __init__(self, st, fwd, actions, bufs):
+    def __init__(self, st, fwd, actions, bufs, masks=None):
         self.st, self.fwd, self.actions, self.bufs = st, fwd, actions, bufs
+        self.masks = masks  # the rows' legal-action words (int32 bits) with masks on the engine
         self.stepped = False  # the optimize op ran: the scalars are its last step's
         self.step_st = None
 
     def vectors(self):
-        """The batch's per-row vectors in acmi_ppo_loss's order."""
-        return self.actions, self.bufs.old_logp, self.bufs.old_values, self.st.targets, self.st.adv
+        """The batch's per-row vectors in acmi_ppo_loss's order (with legal-action masks
+        on the engine the rows' words follow as a sixth)."""
+        v = self.actions, self.bufs.old_logp, self.bufs.old_values, self.st.targets, self.st.adv
+        return v if self.masks is None else v + (self.masks,)
 
 
 class _PPOBuffers(object):
@@ -301,14 +312,15 @@ class _PPOBuffers(object):
 class _PPORowBuffers(object):
     """The shuffled copy of an M-row batch that ``minibatch='rows'`` fills once per epoch
     (acmi_gather_rows): observations (M x 28224 bytes) and the five per-row vectors in
-    :meth:`_PPORun.vectors`' order."""
+    :meth:`_PPORun.vectors`' order (``masked``: and the rows' legal-action words)."""
 
-    def __init__(self, eng, M):
+    def __init__(self, eng, M, masked=False):
         from actorcritic._engine import OBS_SHAPE
         dev = eng.device
         f = lambda: torch.zeros(M, dtype=torch.float32, device=dev)
+        i = lambda: torch.zeros(M, dtype=torch.int32, device=dev)
         self.obs = torch.zeros((M,) + tuple(OBS_SHAPE), dtype=torch.uint8, device=dev)
-        self.vecs = (torch.zeros(M, dtype=torch.int32, device=dev), f(), f(), f(), f())
+        self.vecs = (i(), f(), f(), f(), f()) + ((i(),) if masked else ())
         self.dst = (_lib.c_vp * len(self.vecs))(*[v.data_ptr() for v in self.vecs])
 
     def gather(self, eng, run, index):
@@ -316,6 +328,7 @@ class _PPORowBuffers(object):
         from actorcritic._engine import OBS_BYTES
         M = self.obs.shape[0]
         src = run.vectors()
+        assert len(src) == len(self.vecs)
         assert all(a.dtype == b.dtype and a.numel() == M for a, b in zip(src, self.vecs))
         src_ptrs = (_lib.c_vp * len(src))(*[_lib.ptr(v).value for v in src])
         _lib.call('acmi_gather_rows', _lib.ptr(run.fwd.obs), OBS_BYTES, M, _lib.ptr(index), M, _lib.ptr(self.obs),
@@ -343,10 +356,15 @@ class _PPOBatch(Node):
         bufs = obj._buffers.get(M)
         if bufs is None:
             bufs = obj._buffers[M] = _PPOBuffers(eng, M)
-        _lib.call('acmi_categorical', _lib.ptr(fwd.flat_logits), eng.A, M, eng.A, _lib.ptr(actions), None,
-                  _lib.ptr(bufs.old_logp), eng.stream())
+        masks = fwd.row_masks()
+        if masks is not None:
+            _lib.call('acmi_categorical_masked', _lib.ptr(fwd.flat_logits), eng.A, M, eng.A, _lib.ptr(actions),
+                      _lib.ptr(masks), None, _lib.ptr(bufs.old_logp), eng.stream())
+        else:
+            _lib.call('acmi_categorical', _lib.ptr(fwd.flat_logits), eng.A, M, eng.A, _lib.ptr(actions), None,
+                      _lib.ptr(bufs.old_logp), eng.stream())
         bufs.old_values.copy_(fwd.flat_value)
-        return _PPORun(st, fwd, actions, bufs)
+        return _PPORun(st, fwd, actions, bufs, masks)
 
 
 class _PPOLoss(Node):
@@ -439,10 +457,19 @@ class PPOObjective(ActorCriticObjective):
     def _launch_loss(self, fwd, vectors, row0, rows, bufs, dhead, loss_out, clip_frac_out):
         """acmi_ppo_loss of ``fwd``, a forward of the rows row0 .. row0+rows-1 of the batch
         whose (actions, old_logp, old_values, targets, adv) ``vectors`` are: the run's
-        own (:meth:`_PPORun.vectors`) or their shuffled copy (:class:`_PPORowBuffers`)."""
+        own (:meth:`_PPORun.vectors`) or their shuffled copy (:class:`_PPORowBuffers`);
+        a sixth vector holds the rows' legal-action words: acmi_ppo_loss_masked."""
         eng = self._model.engine
         sl = slice(row0, row0 + rows)
-        actions, old_logp, old_values, targets, adv = (v[sl] for v in vectors)
+        actions, old_logp, old_values, targets, adv = (v[sl] for v in vectors[:5])
+        if len(vectors) > 5:
+            _lib.call('acmi_ppo_loss_masked', _lib.ptr(fwd.flat_logits), eng.A, _lib.ptr(fwd.flat_value),
+                      _lib.ptr(actions), _lib.ptr(old_logp), _lib.ptr(old_values),
+                      _lib.ptr(targets), _lib.ptr(adv), rows, eng.A, self._clip, self._vclip,
+                      self._beta, float(self._vcoef), 1.0 / eng.world_size, _lib.ptr(dhead), eng.ldh,
+                      _lib.ptr(bufs.loss_ws(eng, rows)), _lib.ptr(loss_out), _lib.ptr(clip_frac_out),
+                      _lib.ptr(vectors[5][sl]), _lib.ptr(eng._mask_bad_rows), eng.stream())
+            return
         _lib.call('acmi_ppo_loss', _lib.ptr(fwd.flat_logits), eng.A, _lib.ptr(fwd.flat_value),
                   _lib.ptr(actions), _lib.ptr(old_logp), _lib.ptr(old_values),
                   _lib.ptr(targets), _lib.ptr(adv), rows, eng.A, self._clip, self._vclip,
@@ -621,9 +648,10 @@ class PPOOptimizeOp(Node):
                 raise ValueError('ppo_row_order must return indices into range({}) for every epoch'.format(M))
         # one upload for the run's epochs: a copy from pageable memory waits for the stream
         index = torch.from_numpy(np.stack(order)).to(eng.device)
-        sh = obj._row_buffers.get(M)
+        masked = run.masks is not None
+        sh = obj._row_buffers.get((M, masked) if masked else M)
         if sh is None:
-            sh = obj._row_buffers[M] = _PPORowBuffers(eng, M)
+            sh = obj._row_buffers[(M, masked) if masked else M] = _PPORowBuffers(eng, M, masked)
         st = None
         for epoch in range(len(order)):
             sh.gather(eng, run, index[epoch])

@@ -25,6 +25,13 @@ void set_error(const char* fmt, ...);
     }                                        \
   } while (0)
 
+// the masked entry points' common argument check: a mask and at most 32 actions
+#define ACMI_REQUIRE_MASK(name, legal, A)                                                                     \
+  do {                                                                                                        \
+    ACMI_REQUIRE((legal) != nullptr, ACMI_ERR_ARG, name ": legal is NULL (call the unmasked entry point)");  \
+    ACMI_REQUIRE((A) <= 32, ACMI_ERR_ARG, name ": num_actions=%d, a legal-action mask holds at most 32", (A)); \
+  } while (0)
+
 #define ACMI_LAUNCH_CHECK(what)                                              \
   do {                                                                       \
     hipError_t e_ = hipGetLastError();                                       \

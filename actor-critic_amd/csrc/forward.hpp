@@ -66,10 +66,13 @@ struct EpiAct {
 // the env step, with the arithmetic of heads_kernel / sample_kernel /
 // env_step_kernel (same per-element orders), so the fused step is bit-identical
 // to the three launches it replaces.
+// legal (acmi_rollout_step_masked; nullptr: unmasked): env b's legal-action word
+// at legal[b] -- one more load on the thread that draws, nothing else changes
 struct TailArgs {
   acmi_rollout_io_t io;
   const uint8_t* obs;
   long long img_stride;
+  const uint32_t* legal = nullptr;
 };
 constexpr int kMaxHeads = 32;
 // sx [512], sl [kMaxHeads], s_action: the block's scratch in LDS; mirror
@@ -158,8 +161,9 @@ __device__ __forceinline__ void rollout_tail_body(
     }
     const uint32_t ctr = io.counter + (io.counter_dev ? *io.counter_dev : 0u);
     bool bad;
-    const int y = sample_row(sl, A, io.seed, io.stream_id, ctr, (uint32_t)(row + io.row_offset),
-                             nullptr, 0, &bad);
+    const uint32_t grow = (uint32_t)(row + io.row_offset);
+    const int y = ta.legal ? sample_row<true>(sl, A, io.seed, io.stream_id, ctr, grow, nullptr, 0, &bad, ta.legal[row])
+                           : sample_row<false>(sl, A, io.seed, io.stream_id, ctr, grow, nullptr, 0, &bad);
     if (writer) {
       if (bad) atomicAdd(io.bad_rows, 1);
       io.actions[(long long)row * io.ld] = y;

@@ -517,29 +517,41 @@ static int backward_impl(const Layout& L, const float* P, const uint8_t* obs,
 
 // sampled-loss output gradients at the heads (kfac "gradients" mode):
 // g_pi = softmax(z) - onehot(y), y ~ Cat(z);  g_v = V - y_v = -eps, eps~N(0,1)
-__global__ void sampled_head_grad_kernel(const float* logits, int ld, int B, int A,
-                                         uint32_t seed, uint32_t row0, uint32_t ctr,
-                                         float* g, int ldg) {
+// MASKED (acmi_kfac_output_stats_masked): y ~ Cat over the row's legal set S with
+// the same key, p - onehot(y) on S and +0 elsewhere (stepper.hpp legal_at)
+template <bool MASKED>
+__device__ __forceinline__ void sampled_head_grad_body(const float* logits, int ld, int B, int A,
+                                                       uint32_t seed, uint32_t row0, uint32_t ctr,
+                                                       float* g, int ldg, const uint32_t* legal) {
   const int m = blockIdx.x * blockDim.x + threadIdx.x;
   if (m >= B) return;
   const float* z = logits + (long long)m * ld;
+  const uint32_t lg = MASKED ? legal_bits(legal[m], A) : 0xFFFFFFFFu;
   float mx = -INFINITY;
-  for (int a = 0; a < A; ++a) mx = fmaxf(mx, z[a]);
+  int last = MASKED ? -1 : A - 1;
+  for (int a = 0; a < A; ++a) {
+    if (!legal_at<MASKED>(lg, a)) continue;
+    if (MASKED) last = a;
+    mx = fmaxf(mx, z[a]);
+  }
   float se = 0.f;
-  for (int a = 0; a < A; ++a) se += expf(z[a] - mx);
+  for (int a = 0; a < A; ++a)
+    if (legal_at<MASKED>(lg, a)) se += expf(z[a] - mx);
   // keyed by the global row: a data-parallel shard draws what the full batch would
   const uint32_t h = key4(seed, 0u, ctr, row0 + (uint32_t)m);
   const float u = u01(h);
   // inverse CDF draw
   const float target = u * se;
   float c = 0.f;
-  int y = A - 1;
+  int y = last;
   for (int a = 0; a < A; ++a) {
+    if (!legal_at<MASKED>(lg, a)) continue;
     c += expf(z[a] - mx);
     if (target < c) { y = a; break; }
   }
   float* gr = g + (long long)m * ldg;
-  for (int a = 0; a < A; ++a) gr[a] = expf(z[a] - mx) / se - (a == y ? 1.f : 0.f);
+  for (int a = 0; a < A; ++a)
+    gr[a] = legal_at<MASKED>(lg, a) ? expf(z[a] - mx) / se - (a == y ? 1.f : 0.f) : 0.f;
   // Box-Muller from two further counters
   const float u1 = u01(mix32(h ^ 0x68e31da4U)) + (1.0f / 33554432.0f);
   const float u2 = u01(mix32(h ^ 0xb5297a4dU));
@@ -547,13 +559,25 @@ __global__ void sampled_head_grad_kernel(const float* logits, int ld, int B, int
   gr[A] = -eps;
   for (int a = A + 1; a < ldg; ++a) gr[a] = 0.f;
 }
+__global__ void sampled_head_grad_kernel(const float* logits, int ld, int B, int A,
+                                         uint32_t seed, uint32_t row0, uint32_t ctr,
+                                         float* g, int ldg) {
+  sampled_head_grad_body<false>(logits, ld, B, A, seed, row0, ctr, g, ldg, nullptr);
+}
+__global__ void sampled_head_grad_masked_kernel(const float* logits, int ld, int B, int A,
+                                                uint32_t seed, uint32_t row0, uint32_t ctr,
+                                                float* g, int ldg, const uint32_t* legal) {
+  sampled_head_grad_body<true>(logits, ld, B, A, seed, row0, ctr, g, ldg, legal);
+}
 
 template <int C3>
 static int output_stats_impl(const Layout& L, const float* P, int B,
                              const acmi_acts_t* a, const acmi_bwd_t* bw,
                              uint32_t seed, uint32_t row0, uint32_t ctr,
                              float* gstat, float* ws, long long ws_cap,
-                             hipStream_t s, const char* prep, int stage = 0) {
+                             hipStream_t s, const char* prep, int stage = 0,
+                             const uint32_t* legal = nullptr) {
+  // legal (nullable): per-row legal-action words, the masked head gradients
   // stage: 0 the whole chain; 2 only the G factors, from what backward_stacked_impl
   // left in bw (d2..d4) and in this workspace (scratch maxima, conv1's Gram partials)
   const int ldg = (int)head_grad_ldg(L.A);
@@ -567,8 +591,12 @@ static int output_stats_impl(const Layout& L, const float* P, int B,
   const bool g1_fits = (long long)convt2_gram_blocks(B) * 33 * 32 <= cap;
   int rc = ACMI_OK;
   if (stage == 0) {
-    hipLaunchKernelGGL(sampled_head_grad_kernel, dim3(cdiv(B, 128)), dim3(128), 0, s,
-                       a->logits, a->ld_logits, B, L.A, seed, row0, ctr, ghead, ldg);
+    if (legal)
+      hipLaunchKernelGGL(sampled_head_grad_masked_kernel, dim3(cdiv(B, 128)), dim3(128), 0, s,
+                         a->logits, a->ld_logits, B, L.A, seed, row0, ctr, ghead, ldg, legal);
+    else
+      hipLaunchKernelGGL(sampled_head_grad_kernel, dim3(cdiv(B, 128)), dim3(128), 0, s,
+                         a->logits, a->ld_logits, B, L.A, seed, row0, ctr, ghead, ldg);
     rc = dx_chain<C3>(L, P, B, a, bw, ghead, ldg, s, prep, g1_fits ? part : nullptr, &g1_done, dxs);
     if (rc) return rc;
   } else {
@@ -858,9 +886,10 @@ int acmi_forward_strided(const acmi_net_t* net, const uint8_t* obs, int64_t img_
   return forward_dispatch(net, obs, img_stride, B, acts, want_value, act_img_stride, stream);
 }
 
-int acmi_rollout_step(const acmi_net_t* net, const uint8_t* obs, int64_t img_stride, int B,
-                      const acmi_acts_t* acts, int64_t act_img_stride, const acmi_rollout_io_t* io,
-                      acmi_stream_t stream) {
+// acmi_rollout_step / acmi_rollout_step_masked (legal: nullptr / one word per env)
+static int rollout_step_impl(const acmi_net_t* net, const uint8_t* obs, int64_t img_stride, int B,
+                             const acmi_acts_t* acts, int64_t act_img_stride, const acmi_rollout_io_t* io,
+                             const uint32_t* legal, acmi_stream_t stream) {
   ACMI_REQUIRE(net_modes_ok(net), ACMI_ERR_ARG, "acmi_rollout_step: bad acmi_net_t mode fields");
   const ModeScope mode_scope(net);
   ACMI_REQUIRE(io && io->actions && io->bad_rows && io->obs_out && io->rewards && io->terminals &&
@@ -872,8 +901,22 @@ int acmi_rollout_step(const acmi_net_t* net, const uint8_t* obs, int64_t img_str
                "in %d floats of LDS); step wider action sets with acmi_forward_strided + acmi_sample_actions_dev + "
                "acmi_env_step",
                net->num_actions, kMaxHeads - 1, kMaxHeads);
-  TailArgs ta{*io, obs, (long long)img_stride};
+  TailArgs ta{*io, obs, (long long)img_stride, legal};
   return forward_dispatch(net, obs, img_stride, B, acts, 1, act_img_stride, stream, &ta);
+}
+
+int acmi_rollout_step(const acmi_net_t* net, const uint8_t* obs, int64_t img_stride, int B,
+                      const acmi_acts_t* acts, int64_t act_img_stride, const acmi_rollout_io_t* io,
+                      acmi_stream_t stream) {
+  return rollout_step_impl(net, obs, img_stride, B, acts, act_img_stride, io, nullptr, stream);
+}
+
+int acmi_rollout_step_masked(const acmi_net_t* net, const uint8_t* obs, int64_t img_stride, int B,
+                             const acmi_acts_t* acts, int64_t act_img_stride, const acmi_rollout_io_t* io,
+                             const uint32_t* legal, acmi_stream_t stream) {
+  ACMI_REQUIRE(net, ACMI_ERR_ARG, "acmi_rollout_step_masked: null net");
+  ACMI_REQUIRE_MASK("acmi_rollout_step_masked", legal, net->num_actions);
+  return rollout_step_impl(net, obs, img_stride, B, acts, act_img_stride, io, legal, stream);
 }
 
 int64_t acmi_forward_ws_floats(int B) {
@@ -980,10 +1023,11 @@ int acmi_stream_wait_backward_dx(acmi_stream_t stream) {
   return ACMI_OK;
 }
 
-int acmi_kfac_output_stats(const acmi_net_t* net, int B, const acmi_acts_t* acts,
-                           const acmi_bwd_t* bwd, uint32_t seed, uint32_t row_offset,
-                           uint32_t counter, float* g_stats, float* ws, int64_t ws_floats,
-                           acmi_stream_t stream) {
+// acmi_kfac_output_stats / acmi_kfac_output_stats_masked (legal: nullptr / one word per row)
+static int output_stats_entry(const acmi_net_t* net, int B, const acmi_acts_t* acts,
+                              const acmi_bwd_t* bwd, uint32_t seed, uint32_t row_offset,
+                              uint32_t counter, float* g_stats, float* ws, int64_t ws_floats,
+                              const uint32_t* legal, acmi_stream_t stream) {
   ACMI_REQUIRE(net_modes_ok(net), ACMI_ERR_ARG, "acmi_kfac_output_stats: bad acmi_net_t mode fields");
   const ModeScope mode_scope(net);
   Layout L;
@@ -998,9 +1042,25 @@ int acmi_kfac_output_stats(const acmi_net_t* net, int B, const acmi_acts_t* acts
   hipStream_t s = (hipStream_t)stream;
   if (L.C3 == 32)
     return output_stats_impl<32>(L, net->params, B, acts, bwd, seed, row_offset, counter,
-                                 g_stats, ws, ws_floats, s, static_cast<const char*>(net->conv_prep));
+                                 g_stats, ws, ws_floats, s, static_cast<const char*>(net->conv_prep), 0, legal);
   return output_stats_impl<64>(L, net->params, B, acts, bwd, seed, row_offset, counter, g_stats,
-                               ws, ws_floats, s, static_cast<const char*>(net->conv_prep));
+                               ws, ws_floats, s, static_cast<const char*>(net->conv_prep), 0, legal);
+}
+
+int acmi_kfac_output_stats(const acmi_net_t* net, int B, const acmi_acts_t* acts,
+                           const acmi_bwd_t* bwd, uint32_t seed, uint32_t row_offset,
+                           uint32_t counter, float* g_stats, float* ws, int64_t ws_floats,
+                           acmi_stream_t stream) {
+  return output_stats_entry(net, B, acts, bwd, seed, row_offset, counter, g_stats, ws, ws_floats, nullptr, stream);
+}
+
+int acmi_kfac_output_stats_masked(const acmi_net_t* net, int B, const acmi_acts_t* acts,
+                                  const acmi_bwd_t* bwd, uint32_t seed, uint32_t row_offset,
+                                  uint32_t counter, const uint32_t* legal, float* g_stats, float* ws,
+                                  int64_t ws_floats, acmi_stream_t stream) {
+  ACMI_REQUIRE(net, ACMI_ERR_ARG, "acmi_kfac_output_stats_masked: null net");
+  ACMI_REQUIRE_MASK("acmi_kfac_output_stats_masked", legal, net->num_actions);
+  return output_stats_entry(net, B, acts, bwd, seed, row_offset, counter, g_stats, ws, ws_floats, legal, stream);
 }
 
 int acmi_prof_enable(int site, int capacity) {

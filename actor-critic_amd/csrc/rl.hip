@@ -15,40 +15,90 @@ namespace acmi {
 // row_offset: global row index of local row 0 (a batch sampled in pieces draws
 // the same uniforms as in one launch)
 // ctr_dev (nullable): device counter base added to ctr (graph-replayed rollouts)
-__global__ void sample_kernel(const float* logits, int ld, int B, int A, uint32_t seed,
-                              uint32_t sid, uint32_t ctr, const uint32_t* ctr_dev,
-                              uint32_t row_offset, const float* uniforms, int mode,
-                              int32_t* actions, int32_t* bad) {
+// MASKED (the *_masked kernels below): legal[m] is row m's legal-action word
+// (stepper.hpp legal_at); the unmasked kernels are the MASKED = false bodies.
+template <bool MASKED>
+__device__ __forceinline__ void sample_body(const float* logits, int ld, int B, int A, uint32_t seed,
+                                            uint32_t sid, uint32_t ctr, const uint32_t* ctr_dev,
+                                            uint32_t row_offset, const float* uniforms, int mode,
+                                            int32_t* actions, int32_t* bad, const uint32_t* legal) {
   const int m = blockIdx.x * blockDim.x + threadIdx.x;
   if (m >= B) return;
   if (ctr_dev) ctr += *ctr_dev;
   bool bad_row;
-  const int y = sample_row(logits + (long long)m * ld, A, seed, sid, ctr, (uint32_t)m + row_offset,
-                           uniforms ? uniforms + m : nullptr, mode, &bad_row);
+  const int y = sample_row<MASKED>(logits + (long long)m * ld, A, seed, sid, ctr, (uint32_t)m + row_offset,
+                                   uniforms ? uniforms + m : nullptr, mode, &bad_row,
+                                   MASKED ? legal[m] : 0xFFFFFFFFu);
   if (bad_row) atomicAdd(bad, 1);
   actions[m] = y;
 }
+__global__ void sample_kernel(const float* logits, int ld, int B, int A, uint32_t seed,
+                              uint32_t sid, uint32_t ctr, const uint32_t* ctr_dev,
+                              uint32_t row_offset, const float* uniforms, int mode,
+                              int32_t* actions, int32_t* bad) {
+  sample_body<false>(logits, ld, B, A, seed, sid, ctr, ctr_dev, row_offset, uniforms, mode, actions, bad, nullptr);
+}
+__global__ void sample_masked_kernel(const float* logits, int ld, int B, int A, uint32_t seed,
+                                     uint32_t sid, uint32_t ctr, const uint32_t* ctr_dev,
+                                     uint32_t row_offset, const float* uniforms, int mode,
+                                     int32_t* actions, int32_t* bad, const uint32_t* legal) {
+  sample_body<true>(logits, ld, B, A, seed, sid, ctr, ctr_dev, row_offset, uniforms, mode, actions, bad, legal);
+}
+
+// A row's log-sum-exp and entropy over its legal set S (all of 0..A-1 unmasked):
+//   mx = max_S z, se = sum_S expf(z - mx), lse = mx + logf(se), H = -sum_S p log p
+// in ascending a -- the one statement of the arithmetic every loss kernel shares.
+template <bool MASKED>
+__device__ __forceinline__ float row_lse(const float* z, int A, uint32_t lg) {
+  float mx = -INFINITY;
+  for (int a = 0; a < A; ++a)
+    if (legal_at<MASKED>(lg, a)) mx = fmaxf(mx, z[a]);
+  float se = 0.f;
+  for (int a = 0; a < A; ++a)
+    if (legal_at<MASKED>(lg, a)) se += expf(z[a] - mx);
+  return mx + logf(se);
+}
+template <bool MASKED>
+__device__ __forceinline__ float row_entropy(const float* z, int A, uint32_t lg, float lse) {
+  float H = 0.f;
+  for (int a = 0; a < A; ++a) {
+    if (!legal_at<MASKED>(lg, a)) continue;
+    const float lp = z[a] - lse;
+    H -= expf(lp) * lp;
+  }
+  return H;
+}
+// MASKED: is `act` a member of S?  (an empty S has no member)
+template <bool MASKED>
+__device__ __forceinline__ bool action_ok(uint32_t lg, int act, int A) {
+  if constexpr (MASKED) return act >= 0 && act < A && ((lg >> act) & 1u) != 0u;
+  return true;
+}
 
 // per-row entropy and log pi(a) (Categorical.entropy / log_prob, policies.py:87-89)
-__global__ void categorical_kernel(const float* logits, int ld, int B, int A, const int32_t* actions,
-                                   float* ent, float* lpa) {
+// MASKED: over S; log pi of an action outside S is -inf (an empty S: H = 0)
+template <bool MASKED>
+__device__ __forceinline__ void categorical_body(const float* logits, int ld, int B, int A,
+                                                 const int32_t* actions, float* ent, float* lpa,
+                                                 const uint32_t* legal) {
   const int m = blockIdx.x * blockDim.x + threadIdx.x;
   if (m >= B) return;
   const float* z = logits + (long long)m * ld;
-  float mx = -INFINITY;
-  for (int a = 0; a < A; ++a) mx = fmaxf(mx, z[a]);
-  float se = 0.f;
-  for (int a = 0; a < A; ++a) se += expf(z[a] - mx);
-  const float lse = mx + logf(se);
-  if (ent) {
-    float H = 0.f;
-    for (int a = 0; a < A; ++a) {
-      const float lp = z[a] - lse;
-      H -= expf(lp) * lp;
-    }
-    ent[m] = H;
+  const uint32_t lg = MASKED ? legal_bits(legal[m], A) : 0xFFFFFFFFu;
+  const float lse = row_lse<MASKED>(z, A, lg);
+  if (ent) ent[m] = row_entropy<MASKED>(z, A, lg, lse);
+  if (lpa && actions) {
+    const int act = actions[m];
+    lpa[m] = action_ok<MASKED>(lg, act, A) ? z[act] - lse : -INFINITY;
   }
-  if (lpa && actions) lpa[m] = z[actions[m]] - lse;
+}
+__global__ void categorical_kernel(const float* logits, int ld, int B, int A, const int32_t* actions,
+                                   float* ent, float* lpa) {
+  categorical_body<false>(logits, ld, B, A, actions, ent, lpa, nullptr);
+}
+__global__ void categorical_masked_kernel(const float* logits, int ld, int B, int A, const int32_t* actions,
+                                          float* ent, float* lpa, const uint32_t* legal) {
+  categorical_body<true>(logits, ld, B, A, actions, ent, lpa, legal);
 }
 
 // ---------------------------------------------------------------------------
@@ -149,40 +199,49 @@ __global__ void adv_normalize_kernel(float* a, long long M, const double* mom, d
 // ---------------------------------------------------------------------------
 constexpr int LOSS_BLOCK = 256;
 
-__global__ void a2c_loss_kernel(const float* logits, int ld, const float* values,
-                                const int32_t* actions, const float* targets,
-                                const float* adv, int M, int A, float beta, float vcoef,
-                                float gscale, float* dhead, int ldh, float* part) {
+// MASKED: the softmax, entropy and policy columns over S (columns outside S are
+// +0); a bad row -- S empty or the taken action outside S -- adds nothing to the
+// policy and entropy sums, gets zero policy columns, keeps its value term and
+// counts in bad_rows (nullable).
+template <bool MASKED>
+__device__ __forceinline__ void a2c_loss_body(const float* logits, int ld, const float* values,
+                                              const int32_t* actions, const float* targets,
+                                              const float* adv, int M, int A, float beta, float vcoef,
+                                              float gscale, float* dhead, int ldh, float* part,
+                                              const uint32_t* legal, int32_t* bad_rows) {
   __shared__ float red[3][LOSS_BLOCK / 64];
   const int m = blockIdx.x * blockDim.x + threadIdx.x;
   float s_pl = 0.f, s_h = 0.f, s_v = 0.f;
   if (m < M) {
     const float* z = logits + (long long)m * ld;
-    float mx = -INFINITY;
-    for (int a = 0; a < A; ++a) mx = fmaxf(mx, z[a]);
-    float se = 0.f;
-    for (int a = 0; a < A; ++a) se += expf(z[a] - mx);
-    const float lse = mx + logf(se);
-    float H = 0.f;
-    for (int a = 0; a < A; ++a) {
-      const float lp = z[a] - lse;
-      H -= expf(lp) * lp;
-    }
+    const uint32_t lg = MASKED ? legal_bits(legal[m], A) : 0xFFFFFFFFu;
     const int act = actions[m];
-    const float lpa = z[act] - lse;
+    const bool ok = action_ok<MASKED>(lg, act, A);
     const float ad = adv[m];
     const float diff = targets[m] - values[m];
-    s_pl = ad * lpa;
-    s_h = H;
     s_v = 0.5f * diff * diff;
     // dL/dz_k = -(1/M)[adv (onehot_k - p_k) - beta p_k (log p_k + H)]
     const float inv = gscale / (float)M;
     float* g = dhead + (long long)m * ldh;
-    for (int a = 0; a < A; ++a) {
-      const float lp = z[a] - lse;
-      const float p = expf(lp);
-      const float oh = a == act ? 1.f : 0.f;
-      g[a] = -inv * (ad * (oh - p) - beta * p * (lp + H));
+    if (ok) {
+      const float lse = row_lse<MASKED>(z, A, lg);
+      const float H = row_entropy<MASKED>(z, A, lg, lse);
+      const float lpa = z[act] - lse;
+      s_pl = ad * lpa;
+      s_h = H;
+      for (int a = 0; a < A; ++a) {
+        if (!legal_at<MASKED>(lg, a)) {
+          g[a] = 0.f;
+          continue;
+        }
+        const float lp = z[a] - lse;
+        const float p = expf(lp);
+        const float oh = a == act ? 1.f : 0.f;
+        g[a] = -inv * (ad * (oh - p) - beta * p * (lp + H));
+      }
+    } else {
+      for (int a = 0; a < A; ++a) g[a] = 0.f;
+      if (bad_rows) atomicAdd(bad_rows, 1);
     }
     // d(vcoef * L_v)/dV = vcoef * (V - target) / M
     g[A] = vcoef * inv * (values[m] - targets[m]);
@@ -209,6 +268,22 @@ __global__ void a2c_loss_kernel(const float* logits, int ld, const float* values
     part[blockIdx.x * 3 + 1] = b;
     part[blockIdx.x * 3 + 2] = c;
   }
+}
+
+__global__ void a2c_loss_kernel(const float* logits, int ld, const float* values,
+                                const int32_t* actions, const float* targets,
+                                const float* adv, int M, int A, float beta, float vcoef,
+                                float gscale, float* dhead, int ldh, float* part) {
+  a2c_loss_body<false>(logits, ld, values, actions, targets, adv, M, A, beta, vcoef, gscale, dhead, ldh, part,
+                       nullptr, nullptr);
+}
+__global__ void a2c_loss_masked_kernel(const float* logits, int ld, const float* values,
+                                       const int32_t* actions, const float* targets,
+                                       const float* adv, int M, int A, float beta, float vcoef,
+                                       float gscale, float* dhead, int ldh, float* part,
+                                       const uint32_t* legal, int32_t* bad_rows) {
+  a2c_loss_body<true>(logits, ld, values, actions, targets, adv, M, A, beta, vcoef, gscale, dhead, ldh, part,
+                      legal, bad_rows);
 }
 
 __global__ void a2c_loss_final_kernel(const float* part, int nb, int M, float beta,
@@ -243,39 +318,24 @@ __global__ void a2c_loss_final_kernel(const float* part, int nb, int M, float be
 // ---------------------------------------------------------------------------
 constexpr int PPO_SUMS = 5;  // surrogate, entropy, value loss, old_logp - logp, clipped rows
 
-__global__ void ppo_loss_kernel(const float* logits, int ld, const float* values,
-                                const int32_t* actions, const float* old_logp,
-                                const float* old_values, const float* targets, const float* adv,
-                                int M, int A, float clip_eps, float vclip, float beta,
-                                float vcoef, float gscale, float* dhead, int ldh, float* part) {
+// MASKED: as a2c_loss_body; a bad row adds nothing to the surrogate, entropy,
+// KL and clipped-row sums either.
+template <bool MASKED>
+__device__ __forceinline__ void ppo_loss_body(const float* logits, int ld, const float* values,
+                                              const int32_t* actions, const float* old_logp,
+                                              const float* old_values, const float* targets, const float* adv,
+                                              int M, int A, float clip_eps, float vclip, float beta,
+                                              float vcoef, float gscale, float* dhead, int ldh, float* part,
+                                              const uint32_t* legal, int32_t* bad_rows) {
   __shared__ float red[PPO_SUMS][LOSS_BLOCK / 64];
   const int m = blockIdx.x * blockDim.x + threadIdx.x;
   float s_pl = 0.f, s_h = 0.f, s_v = 0.f, s_kl = 0.f, s_cf = 0.f;
   if (m < M) {
     const float* z = logits + (long long)m * ld;
-    float mx = -INFINITY;
-    for (int a = 0; a < A; ++a) mx = fmaxf(mx, z[a]);
-    float se = 0.f;
-    for (int a = 0; a < A; ++a) se += expf(z[a] - mx);
-    const float lse = mx + logf(se);
-    float H = 0.f;
-    for (int a = 0; a < A; ++a) {
-      const float lp = z[a] - lse;
-      H -= expf(lp) * lp;
-    }
+    const uint32_t lg = MASKED ? legal_bits(legal[m], A) : 0xFFFFFFFFu;
     const int act = actions[m];
-    const float lpa = z[act] - lse;
+    const bool ok = action_ok<MASKED>(lg, act, A);
     const float ad = adv[m];
-    const float olp = old_logp[m];
-    const float r = expf(lpa - olp);
-    const float rc = fminf(fmaxf(r, 1.f - clip_eps), 1.f + clip_eps);
-    const float s1 = r * ad, s2 = rc * ad;
-    // the unclipped term is the active minimum (ties: r inside the range, s1 == s2)
-    const bool pol_on = s1 <= s2;
-    s_pl = pol_on ? s1 : s2;
-    s_h = H;
-    s_kl = olp - lpa;
-    s_cf = fabsf(r - 1.f) > clip_eps ? 1.f : 0.f;
     const float v = values[m], tg = targets[m];
     const float diff = tg - v;
     s_v = 0.5f * diff * diff;
@@ -293,15 +353,37 @@ __global__ void ppo_loss_kernel(const float* logits, int ld, const float* values
         }
       }
     }
-    // dL/dz_k = -(1/M)[adv r (onehot_k - p_k) [unclipped] - beta p_k (log p_k + H)]
-    const float w = pol_on ? s1 : 0.f;
     const float inv = gscale / (float)M;
     float* g = dhead + (long long)m * ldh;
-    for (int a = 0; a < A; ++a) {
-      const float lp = z[a] - lse;
-      const float p = expf(lp);
-      const float oh = a == act ? 1.f : 0.f;
-      g[a] = -inv * (w * (oh - p) - beta * p * (lp + H));
+    if (ok) {
+      const float lse = row_lse<MASKED>(z, A, lg);
+      const float H = row_entropy<MASKED>(z, A, lg, lse);
+      const float lpa = z[act] - lse;
+      const float olp = old_logp[m];
+      const float r = expf(lpa - olp);
+      const float rc = fminf(fmaxf(r, 1.f - clip_eps), 1.f + clip_eps);
+      const float s1 = r * ad, s2 = rc * ad;
+      // the unclipped term is the active minimum (ties: r inside the range, s1 == s2)
+      const bool pol_on = s1 <= s2;
+      s_pl = pol_on ? s1 : s2;
+      s_h = H;
+      s_kl = olp - lpa;
+      s_cf = fabsf(r - 1.f) > clip_eps ? 1.f : 0.f;
+      // dL/dz_k = -(1/M)[adv r (onehot_k - p_k) [unclipped] - beta p_k (log p_k + H)]
+      const float w = pol_on ? s1 : 0.f;
+      for (int a = 0; a < A; ++a) {
+        if (!legal_at<MASKED>(lg, a)) {
+          g[a] = 0.f;
+          continue;
+        }
+        const float lp = z[a] - lse;
+        const float p = expf(lp);
+        const float oh = a == act ? 1.f : 0.f;
+        g[a] = -inv * (w * (oh - p) - beta * p * (lp + H));
+      }
+    } else {
+      for (int a = 0; a < A; ++a) g[a] = 0.f;
+      if (bad_rows) atomicAdd(bad_rows, 1);
     }
     // d(vcoef * L_v)/dV = vcoef * (V - target) / M where the unclipped square is active
     const float gv = vcoef * inv * (values[m] - targets[m]);
@@ -327,6 +409,24 @@ __global__ void ppo_loss_kernel(const float* logits, int ld, const float* values
     for (int i = 0; i < LOSS_BLOCK / 64; ++i) a += red[threadIdx.x][i];
     part[blockIdx.x * PPO_SUMS + threadIdx.x] = a;
   }
+}
+
+__global__ void ppo_loss_kernel(const float* logits, int ld, const float* values,
+                                const int32_t* actions, const float* old_logp,
+                                const float* old_values, const float* targets, const float* adv,
+                                int M, int A, float clip_eps, float vclip, float beta,
+                                float vcoef, float gscale, float* dhead, int ldh, float* part) {
+  ppo_loss_body<false>(logits, ld, values, actions, old_logp, old_values, targets, adv, M, A, clip_eps, vclip, beta,
+                       vcoef, gscale, dhead, ldh, part, nullptr, nullptr);
+}
+__global__ void ppo_loss_masked_kernel(const float* logits, int ld, const float* values,
+                                       const int32_t* actions, const float* old_logp,
+                                       const float* old_values, const float* targets, const float* adv,
+                                       int M, int A, float clip_eps, float vclip, float beta,
+                                       float vcoef, float gscale, float* dhead, int ldh, float* part,
+                                       const uint32_t* legal, int32_t* bad_rows) {
+  ppo_loss_body<true>(logits, ld, values, actions, old_logp, old_values, targets, adv, M, A, clip_eps, vclip, beta,
+                      vcoef, gscale, dhead, ldh, part, legal, bad_rows);
 }
 
 __global__ void ppo_loss_final_kernel(const float* part, int nb, int M, float beta, float scale,
@@ -582,6 +682,33 @@ int acmi_categorical(const float* logits, int ld, int B, int A, const int32_t* a
   return ACMI_OK;
 }
 
+int acmi_sample_actions_masked(const float* logits, int ld, int B, int A, uint32_t seed,
+                               uint32_t stream_id, const uint32_t* counter_dev, uint32_t counter_add,
+                               int row_offset, const float* uniforms, int mode, const uint32_t* legal,
+                               int32_t* actions, int32_t* bad_rows, acmi_stream_t stream) {
+  ACMI_REQUIRE_MASK("acmi_sample_actions_masked", legal, A);
+  ACMI_REQUIRE(logits && actions && bad_rows && B >= 0 && A >= 1 && ld >= A && row_offset >= 0,
+               ACMI_ERR_ARG, "acmi_sample_actions_masked: bad arguments");
+  if (B == 0) return ACMI_OK;
+  hipLaunchKernelGGL(sample_masked_kernel, dim3(cdiv(B, 256)), dim3(256), 0, (hipStream_t)stream,
+                     logits, ld, B, A, seed, stream_id, counter_add, counter_dev,
+                     (uint32_t)row_offset, uniforms, mode, actions, bad_rows, legal);
+  ACMI_LAUNCH_CHECK("acmi_sample_actions_masked");
+  return ACMI_OK;
+}
+
+int acmi_categorical_masked(const float* logits, int ld, int B, int A, const int32_t* actions,
+                            const uint32_t* legal, float* entropy, float* log_prob, acmi_stream_t stream) {
+  ACMI_REQUIRE_MASK("acmi_categorical_masked", legal, A);
+  ACMI_REQUIRE(logits && B >= 0 && A >= 1 && ld >= A && (entropy || log_prob) && (!log_prob || actions),
+               ACMI_ERR_ARG, "acmi_categorical_masked: bad arguments");
+  if (B == 0) return ACMI_OK;
+  hipLaunchKernelGGL(categorical_masked_kernel, dim3(cdiv(B, 256)), dim3(256), 0, (hipStream_t)stream, logits,
+                     ld, B, A, actions, entropy, log_prob, legal);
+  ACMI_LAUNCH_CHECK("acmi_categorical_masked");
+  return ACMI_OK;
+}
+
 int acmi_returns(const float* rewards, const uint8_t* terminals, const float* values,
                  const float* v_boot, int N, int T, const float* gamma_pow,
                  const float* boot_pow, float* targets, float* adv, acmi_stream_t stream) {
@@ -648,6 +775,24 @@ int acmi_a2c_loss(const float* logits, int ld, const float* values, const int32_
   return ACMI_OK;
 }
 
+int acmi_a2c_loss_masked(const float* logits, int ld, const float* values, const int32_t* actions,
+                         const float* targets, const float* adv, int M, int A, float beta, float vcoef,
+                         float grad_scale, float* dhead, int ldh, float* ws, float* loss_out,
+                         const uint32_t* legal, int32_t* bad_rows, acmi_stream_t stream) {
+  ACMI_REQUIRE_MASK("acmi_a2c_loss_masked", legal, A);
+  ACMI_REQUIRE(logits && values && actions && targets && adv && dhead && ws && loss_out &&
+                   M > 0 && A >= 1 && ld >= A && ldh >= A + 1,
+               ACMI_ERR_ARG, "acmi_a2c_loss_masked: bad arguments");
+  const int nb = cdiv(M, LOSS_BLOCK);
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(a2c_loss_masked_kernel, dim3(nb), dim3(LOSS_BLOCK), 0, s, logits, ld, values,
+                     actions, targets, adv, M, A, beta, vcoef, grad_scale, dhead, ldh, ws, legal, bad_rows);
+  hipLaunchKernelGGL(a2c_loss_final_kernel, dim3(1), dim3(64), 0, s, ws, nb, M, beta,
+                     grad_scale, loss_out);
+  ACMI_LAUNCH_CHECK("acmi_a2c_loss_masked");
+  return ACMI_OK;
+}
+
 int64_t acmi_ppo_loss_ws_floats(int M) { return (long long)PPO_SUMS * cdiv(M, LOSS_BLOCK) + 16; }
 
 int acmi_ppo_loss(const float* logits, int ld, const float* values, const int32_t* actions,
@@ -667,6 +812,28 @@ int acmi_ppo_loss(const float* logits, int ld, const float* values, const int32_
   hipLaunchKernelGGL(ppo_loss_final_kernel, dim3(1), dim3(64), 0, s, ws, nb, M, beta, grad_scale,
                      loss_out, clip_frac_out);
   ACMI_LAUNCH_CHECK("acmi_ppo_loss");
+  return ACMI_OK;
+}
+
+int acmi_ppo_loss_masked(const float* logits, int ld, const float* values, const int32_t* actions,
+                         const float* old_logp, const float* old_values, const float* targets,
+                         const float* adv, int M, int A, float clip_eps, float vclip, float beta,
+                         float vcoef, float grad_scale, float* dhead, int ldh, float* ws, float* loss_out,
+                         float* clip_frac_out, const uint32_t* legal, int32_t* bad_rows,
+                         acmi_stream_t stream) {
+  ACMI_REQUIRE_MASK("acmi_ppo_loss_masked", legal, A);
+  ACMI_REQUIRE(logits && values && actions && old_logp && targets && adv && dhead && ws &&
+                   loss_out && M > 0 && A >= 1 && ld >= A && ldh >= A + 1 && clip_eps > 0.f &&
+                   (old_values || !(vclip > 0.f)),
+               ACMI_ERR_ARG, "acmi_ppo_loss_masked: bad arguments");
+  const int nb = cdiv(M, LOSS_BLOCK);
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(ppo_loss_masked_kernel, dim3(nb), dim3(LOSS_BLOCK), 0, s, logits, ld, values, actions,
+                     old_logp, old_values, targets, adv, M, A, clip_eps, vclip, beta, vcoef,
+                     grad_scale, dhead, ldh, ws, legal, bad_rows);
+  hipLaunchKernelGGL(ppo_loss_final_kernel, dim3(1), dim3(64), 0, s, ws, nb, M, beta, grad_scale,
+                     loss_out, clip_frac_out);
+  ACMI_LAUNCH_CHECK("acmi_ppo_loss_masked");
   return ACMI_OK;
 }
 

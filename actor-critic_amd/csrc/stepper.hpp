@@ -22,10 +22,12 @@ __device__ __forceinline__ uint32_t word_hash(uint32_t base, uint32_t g) {
 // Mixed-game synthetic Atari-57 (BASELINE configs[4]; the reference's MultiEnv
 // holds one game, multi_env.py:36-47).  Env n plays game st.game[n] (index into
 // the Atari-57 list, wrappers.ATARI57); a null game array = every env the
-// default game (Breakout's dynamics, no action masking).  A game fixes its
+// default game (Breakout's dynamics, every action distinct).  A game fixes its
 // dynamics salt (XORed into the seed: its own frames, rewards and lengths), its
 // episode-length range, its +-1 reward rates and its legal-action count under
-// the full 18-action set (actions past it act as NOOP, as in ALE).  Breakout's
+// the full 18-action set (actions past it act as NOOP, as in ALE; a policy under
+// legal-action masks -- sample_row<true> below, wrappers.legal_action_masks -- never
+// emits one).  Breakout's
 // entry is the default game's dynamics.  Restated in oracle.game_params.
 constexpr int kNumGames = 57;
 constexpr int kGameBreakout = 12;
@@ -269,30 +271,54 @@ __device__ __forceinline__ void env_step_block(acmi_env_state_t st, int n, uint3
   env_step_block_pre(st, n, e, seed, action, pre, obs_out, rewards, terminals, ep_rewards, ld);
 }
 
+// Legal-action masks: one uint32 per row, bit a set = action a is
+// legal; S = the legal a < A (A <= 32 with a mask).  The masked kernels are the
+// unmasked ones with this test added -- MASKED false compiles it away -- so a mask
+// with the low A bits set reproduces the unmasked bytes.
+__device__ __forceinline__ uint32_t legal_bits(uint32_t legal, int A) {
+  return A >= 32 ? legal : legal & ((1u << A) - 1u);
+}
+template <bool MASKED>
+__device__ __forceinline__ bool legal_at(uint32_t lg, int a) {
+  if constexpr (MASKED) return ((lg >> a) & 1u) != 0u;
+  return true;
+}
+
 // Categorical draw over the A logits z[0..A) (inverse CDF of softmax in f32
 // with u = u01(key4(seed, sid, ctr, row)) or the given u); -1 for a row with a
 // non-finite logit (*bad_flag set).  mode: argmax.
+// MASKED: the maximum, the sums, the draw and the mode run over S only (the
+// non-finite check stays over all A logits); the draw's fallback is the last
+// legal action; an empty S is a bad row (-1) as well.
+template <bool MASKED = false>
 __device__ __forceinline__ int sample_row(const float* z, int A, uint32_t seed, uint32_t sid,
                                           uint32_t ctr, uint32_t row, const float* u_given,
-                                          int mode, bool* bad_flag) {
+                                          int mode, bool* bad_flag, uint32_t legal = 0xFFFFFFFFu) {
+  const uint32_t lg = MASKED ? legal_bits(legal, A) : 0xFFFFFFFFu;
   float mx = -INFINITY;
   bool finite = true;
   int amax = 0;
+  int last = MASKED ? -1 : A - 1;
   for (int a = 0; a < A; ++a) {
     const float v = z[a];
     finite = finite && isfinite(v);
+    if (!legal_at<MASKED>(lg, a)) continue;
+    if (MASKED) last = a;
     if (v > mx) { mx = v; amax = a; }
   }
-  *bad_flag = !finite;
-  if (!finite) return -1;
+  const bool bad = !finite || (MASKED && lg == 0u);
+  *bad_flag = bad;
+  if (bad) return -1;
   if (mode) return amax;  // first maximal index, like argmax
   float se = 0.f;
-  for (int a = 0; a < A; ++a) se += expf(z[a] - mx);
+  for (int a = 0; a < A; ++a)
+    if (legal_at<MASKED>(lg, a)) se += expf(z[a] - mx);
   const float u = u_given ? *u_given : u01(key4(seed, sid, ctr, row));
   const float target = u * se;
   float c = 0.f;
-  int y = A - 1;
+  int y = last;
   for (int a = 0; a < A; ++a) {
+    if (!legal_at<MASKED>(lg, a)) continue;
     c += expf(z[a] - mx);
     if (target < c) { y = a; break; }
   }

@@ -678,6 +678,72 @@ int acmi_rollout_step(const acmi_net_t* net, const uint8_t* obs,
                       acmi_stream_t stream);
 
 /* ------------------------------------------------------------------------
+ * Legal-action masks (invalid-action masking; beyond the reference).  Opt-in:
+ * each entry point below is its unmasked counterpart plus `legal`, device
+ * uint32[rows], bit a of legal[row] set = action a is legal for that row (a
+ * caller with a row offset passes the pointer pre-offset).  S = the legal
+ * a < A; bits at or above A are ignored.  A <= 32 (a larger A, or a NULL
+ * `legal`, is ACMI_ERR_ARG before anything is enqueued; the unmasked entry
+ * points keep 1..64).  Per row, in f32, ascending a, the unmasked kernels'
+ * expressions restricted to S:
+ *   mx = max_S z, se = sum_S expf(z - mx), lse = mx + logf(se),
+ *   p_a = expf(z_a - lse) on S and exactly 0 elsewhere, H = -sum_S p_a (z_a - lse),
+ *   log_prob(a) = z_a - lse on S, -INFINITY elsewhere.
+ * Sampling: inverse CDF over S (target = u * se, the running sum over S
+ * ascending; the fallback is the LAST LEGAL action), mode = first maximal
+ * legal index; the non-finite check covers all A logits; an empty S yields
+ * -1 and counts in bad_rows like a non-finite row.  Gradients: columns
+ * outside S of dhead / the sampled head gradient are +0.0f; an illegal
+ * logit, however large (finite), influences nothing.  Loss kernels: a row
+ * whose S is empty or whose taken action is outside S is a bad row -- it adds
+ * nothing to the policy / entropy (/ PPO KL and clip) sums, gets zero policy
+ * columns, keeps its value term and its share of the 1/M means, and
+ * increments *bad_rows (device int32, nullable); it never produces NaN/inf.
+ * With the low A bits of every word set each entry point produces the bytes
+ * of its unmasked counterpart (the kernels are one template).
+ * ---------------------------------------------------------------------- */
+int acmi_sample_actions_masked(const float* logits, int ld, int B, int A,
+                               uint32_t seed, uint32_t stream_id,
+                               const uint32_t* counter_dev, uint32_t counter_add,
+                               int row_offset, const float* uniforms, int mode,
+                               const uint32_t* legal, int32_t* actions,
+                               int32_t* bad_rows, acmi_stream_t stream);
+int acmi_categorical_masked(const float* logits, int ld, int B, int A,
+                            const int32_t* actions, const uint32_t* legal,
+                            float* entropy, float* log_prob, acmi_stream_t stream);
+/* Workspaces: acmi_a2c_loss_ws_floats / acmi_ppo_loss_ws_floats; the loss
+ * slots and grad_scale are the unmasked calls'.  With old_logp from
+ * acmi_categorical_masked on the same logits and mask the PPO ratio is exactly
+ * 1 and dhead is acmi_a2c_loss_masked's, bit for bit. */
+int acmi_a2c_loss_masked(const float* logits, int ld, const float* values,
+                         const int32_t* actions, const float* targets,
+                         const float* adv, int M, int A, float beta, float vcoef,
+                         float grad_scale, float* dhead, int ldh, float* ws,
+                         float* loss_out, const uint32_t* legal, int32_t* bad_rows,
+                         acmi_stream_t stream);
+int acmi_ppo_loss_masked(const float* logits, int ld, const float* values,
+                         const int32_t* actions, const float* old_logp,
+                         const float* old_values, const float* targets,
+                         const float* adv, int M, int A, float clip_eps, float vclip,
+                         float beta, float vcoef, float grad_scale, float* dhead,
+                         int ldh, float* ws, float* loss_out, float* clip_frac_out,
+                         const uint32_t* legal, int32_t* bad_rows, acmi_stream_t stream);
+/* acmi_kfac_output_stats with y ~ Cat over S (the same RNG key): the sampled
+ * head gradient is p - onehot(y) on S and 0 elsewhere; the value draw is
+ * unchanged.  (acmi_backward_stacked has no masked form.) */
+int acmi_kfac_output_stats_masked(const acmi_net_t* net, int B, const acmi_acts_t* acts,
+                                  const acmi_bwd_t* bwd, uint32_t seed, uint32_t row_offset,
+                                  uint32_t counter, const uint32_t* legal, float* g_stats,
+                                  float* ws, int64_t ws_floats, acmi_stream_t stream);
+/* acmi_rollout_step with env b's draw over legal[b] (one word per env of the
+ * call): bit-identical to acmi_forward_strided + acmi_sample_actions_masked +
+ * acmi_env_step. */
+int acmi_rollout_step_masked(const acmi_net_t* net, const uint8_t* obs,
+                             int64_t img_stride, int B, const acmi_acts_t* acts,
+                             int64_t act_img_stride, const acmi_rollout_io_t* io,
+                             const uint32_t* legal, acmi_stream_t stream);
+
+/* ------------------------------------------------------------------------
  * Building blocks exposed for parity tests and the bench (not needed by a
  * reference-shaped caller).
  * ---------------------------------------------------------------------- */
