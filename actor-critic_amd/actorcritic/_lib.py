@@ -47,6 +47,12 @@ class EnvState(ctypes.Structure):
                 ('game', c_vp)]
 
 
+class GameState(ctypes.Structure):
+    # acmi_game_state_t (its size: acmi_game_state_bytes)
+    _fields_ = [('episode', c_vp), ('step', c_vp), ('total', c_vp), ('done', c_vp), ('vars', c_vp),
+                ('game', ctypes.c_int32)]
+
+
 class RolloutIO(ctypes.Structure):
     _fields_ = [('seed', c_u32), ('stream_id', c_u32), ('counter', c_u32), ('counter_dev', c_vp),
                 ('row_offset', c_int), ('actions', c_vp), ('bad_rows', c_vp), ('state', EnvState),
@@ -148,6 +154,11 @@ _SIGS = {
     'acmi_env_reset': (c_int, [ctypes.POINTER(EnvState), c_int, c_int, c_u32, c_vp, c_i64, c_vp]),
     'acmi_env_step': (c_int, [ctypes.POINTER(EnvState), c_int, c_int, c_u32, c_vp, c_vp, c_i64, c_vp, c_i64,
                               c_vp, c_vp, c_vp, c_i64, c_vp]),
+    'acmi_game_state_ints': (c_int, []),
+    'acmi_game_state_bytes': (c_i64, []),
+    'acmi_game_reset': (c_int, [ctypes.POINTER(GameState), c_int, c_int, c_u32, c_vp, c_i64, c_vp]),
+    'acmi_game_step': (c_int, [ctypes.POINTER(GameState), c_int, c_int, c_u32, c_vp, c_vp, c_i64, c_vp, c_i64,
+                               c_vp, c_vp, c_vp, c_i64, c_vp]),
     'acmi_atari_preprocess': (c_int, [c_vp, c_i64, c_i64, c_vp, c_int, c_int, c_int, c_vp, c_i64, c_vp]),
     'acmi_atari_stack': (c_int, [c_vp, c_i64, c_i64, c_vp, c_int, c_int, c_int, c_vp, c_int, c_vp, c_vp,
                                  c_i64, c_vp]),

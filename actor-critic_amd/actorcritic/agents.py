@@ -69,7 +69,7 @@ class SingleEnvAgent(Agent):
 
 
 class _RolloutBuffers(object):
-    def __init__(self, engine, N, T):
+    def __init__(self, engine, N, T, env=None):
         dev = engine.device
         self.N, self.T = N, T
         self.obs = torch.zeros((N, T, 84, 84, 4), dtype=torch.uint8, device=dev)
@@ -90,9 +90,12 @@ class _RolloutBuffers(object):
         self.ws = [torch.zeros(max(need, 1), dtype=torch.float32, device=dev) for _ in range(2)]
         self.use_graph = os.environ.get('ACMI_ROLLOUT_GRAPH', '0') == '1'
         # the fused step (acmi_rollout_step) takes up to 31 actions; wider action sets
-        # step unfused: forward + sampler + env step, the ACMI_ROLLOUT_FUSED=0 path
+        # step unfused: forward + sampler + env step, the ACMI_ROLLOUT_FUSED=0 path.
+        # So does an env that says ``fused_step = False`` (the fused tail holds the
+        # synthetic stepper: envs.games.DeviceGameEnvs); no such attribute = fused
         self.fused = (os.environ.get('ACMI_ROLLOUT_FUSED', '1') != '0' and
-                      engine.A <= _lib.ROLLOUT_STEP_MAX_ACTIONS)
+                      engine.A <= _lib.ROLLOUT_STEP_MAX_ACTIONS and
+                      bool(getattr(env, 'fused_step', True)))
         # step fusion: step t's tail also runs step t+1's conv tower (needs the
         # fused tower: x3 gemm mode, checked once per rollout, and prepared weights)
         self.fuse_steps = self.fused and os.environ.get('ACMI_ROLLOUT_FUSE_STEPS', '1') != '0'
@@ -235,7 +238,7 @@ class MultiEnvAgent(Agent):
         env = self._env.batched
         N, T = env.num_envs, self._num_steps
         if self._bufs is None or self._bufs.N != N or self._bufs.T != T:
-            self._bufs = _RolloutBuffers(eng, N, T)
+            self._bufs = _RolloutBuffers(eng, N, T, env)
         rb = self._bufs
         if getattr(env, 'host_stepped', False):
             return self._interact_host(eng, env, rb, N, T)

@@ -1,0 +1,204 @@
+"""Device games: small real games that step and render on the GPU.
+
+:class:`DeviceGameEnvs` is a batch of Catch or Breakout envs behind ``acmi_game_step``
+(csrc/games.hip): one HIP workgroup per env advances the game's integer state and
+draws the new 84x84 frame straight into the 4-frame stack, with the synthetic stepper's
+wrapper semantics (lazy auto-reset, FrameStackWrapper, EpisodeInfoWrapper).  It
+duck-types :class:`actorcritic.envs.atari.wrappers.SyntheticAtariEnvs`, so ``MultiEnv``
+and ``MultiEnvAgent`` put it on the device rollout; the rules are those of
+:class:`actorcritic.envs.games.host.HostGame`, bit for bit.
+
+:func:`evaluate` plays whole episodes forward-only and returns their returns.
+"""
+
+import ctypes
+
+import numpy as np
+import torch
+
+from actorcritic import _lib, spaces
+from actorcritic._engine import OBS_BYTES
+from actorcritic.envs.atari.wrappers import EpisodeInfoBatch, _mask_tensor, action_mask_bits
+from actorcritic.envs.games.host import GAME_ACTIONS, GAMES, STATE_INTS, HostGame, game_id
+
+__all__ = ['DeviceGameEnvs', 'HostGame', 'evaluate', 'GAMES', 'GAME_ACTIONS']
+
+MAX_ACTIONS = 64  # the layout's widest policy head
+
+
+class DeviceGameEnvs(object):
+    """A batch of one device game with frame stacking, on one GPU.
+
+    Args:
+        game: 'catch' or 'breakout'.
+        num_envs: environments on this device.
+        num_actions: size of the Discrete action space; default the game's own count
+            (catch 3, breakout 4).  A wider head (up to 64) is allowed: the actions past
+            the own set step as NOOP, and up to 32 ``legal_action_masks`` holds the own
+            set as one word per env (``MultiEnvAgent(mask_actions=True)``).
+        seed: game seed (an episode's start is a pure function of seed, env, episode).
+        env_offset: global id of the first env (data-parallel shards use rank*num_envs).
+    """
+
+    # acmi_rollout_step's tail hard-wires the synthetic stepper: the rollout steps
+    # these envs unfused (forward + sampler + step_into), see agents._RolloutBuffers
+    fused_step = False
+
+    def __init__(self, game, num_envs, num_actions=None, seed=0, env_offset=0, device=None):
+        _lib.require_gpu()
+        self.game_id = game_id(game)
+        self.game = GAMES[self.game_id]
+        self.num_own_actions = GAME_ACTIONS[self.game]
+        num_actions = self.num_own_actions if num_actions is None else int(num_actions)
+        if not self.num_own_actions <= num_actions <= MAX_ACTIONS:
+            raise ValueError('num_actions={} outside [{}, {}] for {}'.format(num_actions, self.num_own_actions,
+                                                                             MAX_ACTIONS, self.game))
+        self.num_envs = int(num_envs)
+        self.seed = int(seed) & 0xFFFFFFFF
+        self.env_offset = int(env_offset)
+        self.device = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
+        self.observation_space = spaces.Box(low=0, high=255, shape=(84, 84, 4), dtype=np.uint8)
+        self.action_space = spaces.Discrete(num_actions)
+        lib = _lib.load()
+        if int(lib.acmi_game_state_ints()) != STATE_INTS or \
+                int(lib.acmi_game_state_bytes()) != ctypes.sizeof(_lib.GameState):
+            raise ImportError('libacmi game state layout mismatch')
+        N = self.num_envs
+        z = lambda dt: torch.zeros(N, dtype=dt, device=self.device)
+        self._episode, self._step = z(torch.int32), z(torch.int32)
+        self._total, self._done = z(torch.float32), z(torch.uint8)
+        self._vars = torch.zeros((N, STATE_INTS), dtype=torch.int32, device=self.device)
+        self.legal_action_masks = None
+        if num_actions <= _lib.MASK_MAX_ACTIONS:
+            word = action_mask_bits(range(self.num_own_actions), num_actions)
+            self.legal_action_masks = _mask_tensor([word] * N, self.device)
+        self._states = {}
+        self.state = self.range_state(0)
+        self._obs = torch.zeros((N, 84, 84, 4), dtype=torch.uint8, device=self.device)
+
+    def _stream(self):
+        return _lib.stream_handle(self.device)
+
+    def range_state(self, n0):
+        """GameState of envs n0.. (pointers at env n0)."""
+        st = self._states.get(n0)
+        if st is None:
+            st = _lib.GameState(self._episode[n0:].data_ptr(), self._step[n0:].data_ptr(),
+                                self._total[n0:].data_ptr(), self._done[n0:].data_ptr(),
+                                self._vars[n0:].data_ptr(), self.game_id)
+            self._states[n0] = st
+        return st
+
+    def state_arrays(self):
+        """Host copies of the per-env state: episode, step, total, done, vars [N, K]."""
+        return tuple(t.cpu().numpy() for t in (self._episode, self._step, self._total, self._done, self._vars))
+
+    def reset_into(self, obs_ptr, stride=OBS_BYTES):
+        _lib.call('acmi_game_reset', ctypes.byref(self.state), self.num_envs, self.env_offset, self.seed,
+                  ctypes.c_void_p(obs_ptr), stride, self._stream())
+
+    def step_into(self, actions_ptr, obs_in_ptr, in_stride, obs_out_ptr, out_stride, rew_ptr, term_ptr, ep_ptr, ld):
+        self.step_range_into(0, self.num_envs, actions_ptr, obs_in_ptr, in_stride, obs_out_ptr, out_stride, rew_ptr,
+                             term_ptr, ep_ptr, ld)
+
+    def step_range_into(self, n0, n, actions_ptr, obs_in_ptr, in_stride, obs_out_ptr, out_stride, rew_ptr,
+                        term_ptr, ep_ptr, ld):
+        """step_into for envs n0 .. n0+n-1 only (every pointer already at env n0)."""
+        if not (0 <= n0 and 0 <= n and n0 + n <= self.num_envs):
+            raise ValueError('envs {} .. {} outside the batch of {}'.format(n0, n0 + n - 1, self.num_envs))
+        _lib.call('acmi_game_step', ctypes.byref(self.range_state(n0)), n, self.env_offset + n0, self.seed,
+                  ctypes.c_void_p(actions_ptr), ctypes.c_void_p(obs_in_ptr), in_stride, ctypes.c_void_p(obs_out_ptr),
+                  out_stride, ctypes.c_void_p(rew_ptr), ctypes.c_void_p(term_ptr), ctypes.c_void_p(ep_ptr), ld,
+                  self._stream())
+
+    # -- gym-like batched API (as SyntheticAtariEnvs) ---------------------------
+    def reset(self):
+        self.reset_into(self._obs.data_ptr())
+        return self._obs.clone()
+
+    def step(self, actions):
+        """actions: [N] ints -> (obs [N,84,84,4] u8, rewards [N], terminals [N] bool, EpisodeInfoBatch)."""
+        a = actions if isinstance(actions, torch.Tensor) else torch.as_tensor(np.asarray(actions))
+        a = a.to(device=self.device, dtype=torch.int32).contiguous()
+        N = self.num_envs
+        rew = torch.empty(N, dtype=torch.float32, device=self.device)
+        term = torch.empty(N, dtype=torch.uint8, device=self.device)
+        ep = torch.empty(N, dtype=torch.float32, device=self.device)
+        self.step_into(a.data_ptr(), self._obs.data_ptr(), OBS_BYTES, self._obs.data_ptr(), OBS_BYTES,
+                       rew.data_ptr(), term.data_ptr(), ep.data_ptr(), 1)
+        return self._obs.clone(), rew, term.view(torch.bool), EpisodeInfoBatch(ep[:, None])
+
+    def close(self):
+        pass
+
+
+def evaluate(model, envs, episodes_per_env, greedy=True, seed=0, uniform=False, return_actions=False,
+             max_steps=None):
+    """Plays ``envs`` (a :class:`DeviceGameEnvs`, reset here -- not the one a training
+    agent is stepping) with ``model``'s policy, forward only: tower forward, sampler
+    (the mode of the policy with ``greedy``, else a draw keyed by ``seed``), step_into;
+    no activations are kept for an update.
+
+    Counts exactly the first ``episodes_per_env`` finished episodes of EVERY env
+    (whichever episodes finish first would favour short ones) and returns their returns,
+    a float32 device tensor [num_envs, episodes_per_env].
+
+    uniform: the actions are drawn uniformly from the game's own set on the host
+        (np.random.RandomState(seed)) and the model is not run (it may be None): the
+        random baseline.
+    return_actions: also returns the actions taken, int32 [steps, num_envs].
+    max_steps: give up (RuntimeError) after that many steps; default
+        episodes_per_env * 2001 (Breakout's step cap + the reset step).
+    """
+    N, E = envs.num_envs, int(episodes_per_env)
+    if E < 1:
+        raise ValueError('episodes_per_env must be at least 1')
+    dev = envs.device
+    limit = int(max_steps) if max_steps is not None else E * 2001
+    obs = torch.zeros((N, 84, 84, 4), dtype=torch.uint8, device=dev)
+    actions = torch.zeros(N, dtype=torch.int32, device=dev)
+    rew = torch.zeros(N, dtype=torch.float32, device=dev)
+    term = torch.zeros(N, dtype=torch.uint8, device=dev)
+    ep = torch.zeros(N, dtype=torch.float32, device=dev)
+    returns = torch.zeros((N, E + 1), dtype=torch.float32, device=dev)  # column E: episodes past the count
+    count = torch.zeros(N, dtype=torch.int64, device=dev)
+    rows = torch.arange(N, device=dev)
+    taken = []
+    rng = np.random.RandomState(seed) if uniform else None
+    eng = None if uniform else model.engine
+    if eng is not None:
+        acts = eng.activations(N, 'evaluate')
+        saved_counter = eng.sample_counter
+    envs.reset_into(obs.data_ptr())
+    steps = 0
+    try:
+        while True:
+            if uniform:
+                actions.copy_(torch.from_numpy(rng.randint(0, envs.num_own_actions, size=N).astype(np.int32)))
+            else:
+                eng.forward(obs.data_ptr(), N, acts.struct, want_value=False)
+                eng.sample_counter = steps  # (a draw is keyed by seed, stream 1 and the step)
+                eng.sample(acts.logits, N, actions, mode=bool(greedy), seed=int(seed) & 0xFFFFFFFF, stream_id=1)
+            if return_actions:
+                taken.append(actions.clone())
+            envs.step_into(actions.data_ptr(), obs.data_ptr(), OBS_BYTES, obs.data_ptr(), OBS_BYTES, rew.data_ptr(),
+                           term.data_ptr(), ep.data_ptr(), 1)
+            done = term != 0
+            slot = torch.where(done, count.clamp(max=E), torch.full_like(count, E))
+            returns[rows, slot] = torch.where(done, ep, returns[rows, slot])
+            count += done
+            steps += 1
+            # one host wait per step; Catch finishes every env at the same step
+            if bool((count >= E).all()):
+                break
+            if steps >= limit:
+                raise RuntimeError('evaluate: {} steps without {} finished episodes in every env'.format(steps, E))
+    finally:
+        if eng is not None:
+            eng.sample_counter = saved_counter  # evaluation does not move the training RNG
+    if eng is not None:
+        eng.check_bad_rows()
+    out = returns[:, :E].contiguous()
+    if return_actions:
+        return out, torch.stack(taken)
+    return out

@@ -23,7 +23,8 @@ from actorcritic.session import Session, get_or_create_global_step, no_op
 
 
 def train_a2c_acktr(acktr, env_id, num_envs, num_steps, checkpoint_path, model_name, summary_path=None,
-                    max_updates=None, seed=0, log_every=10, env_fns=None, mask_actions=False):
+                    max_updates=None, seed=0, log_every=10, env_fns=None, mask_actions=False, game=None,
+                    on_update=None):
     """Trains an Atari model with A2C (RMSProp, conv3 64) or ACKTR (K-FAC, conv3 32).
 
     ``num_envs`` is per GPU; with WORLD_SIZE > 1 (torchrun) every rank steps its own shard.
@@ -33,9 +34,15 @@ def train_a2c_acktr(acktr, env_id, num_envs, num_steps, checkpoint_path, model_n
     ``mask_actions`` (``--mask-actions``): invalid-action masking -- the synthetic game under the
     full 18-action head with its minimal action set as the legal set (host envs: their
     ``legal_action_masks``); actions, losses and K-FAC statistics then run over the legal set.
+    ``game`` (``--game catch|breakout``): a device game (envs.games.DeviceGameEnvs) instead of the
+    synthetic stepper -- something that can be learned; ``env_id`` then only names the results.
+    ``checkpoint_path`` None: nothing is loaded or saved.  ``on_update(updates, model)`` is called
+    after every update (learning curves: scripts/learn_games.py).
     """
     parallel.init_from_env()
-    if env_fns is not None:
+    if game is not None:
+        multi_env = MultiEnv(create_game_environments(game, num_envs, seed=seed, full_action_set=mask_actions))
+    elif env_fns is not None:
         multi_env = create_host_environments(env_fns)
         num_envs = multi_env.num_envs
     else:
@@ -61,7 +68,8 @@ def train_a2c_acktr(acktr, env_id, num_envs, num_steps, checkpoint_path, model_n
     summary_op = no_op()
 
     with Session() as session:
-        load_model(checkpoint_path, model, optimizer, global_step)
+        if checkpoint_path is not None:
+            load_model(checkpoint_path, model, optimizer, global_step)
         step = global_step.value
         updates = 0
         try:
@@ -87,11 +95,13 @@ def train_a2c_acktr(acktr, env_id, num_envs, num_steps, checkpoint_path, model_n
                                            else float(np.nanmean(episode_rewards)))
                     summary_writer.add(step, policy_loss=float(out[3]), baseline_loss=float(out[4]),
                                        policy_entropy=float(out[5]), episode_reward=mean_episode_reward)
-                if step % 100 == 0 and step > 0 and parallel.rank() == 0:
+                if on_update is not None:
+                    on_update(updates, model)
+                if checkpoint_path is not None and step % 100 == 0 and step > 0 and parallel.rank() == 0:
                     save_model(checkpoint_path, model_name, step, model, optimizer)
         except KeyboardInterrupt:
             print('Stop requested')
-            if parallel.rank() == 0:
+            if checkpoint_path is not None and parallel.rank() == 0:
                 save_model(checkpoint_path, model_name, step, model, optimizer)
         finally:
             multi_env.close()
@@ -109,6 +119,14 @@ def create_environments(env_id, num_envs, seed=0, full_action_set=False):
                                            env_offset=parallel.rank() * num_envs)
     return wrappers.SyntheticAtariEnvs(num_envs, num_actions=wrappers.num_actions_for(env_id), seed=seed,
                                        env_offset=parallel.rank() * num_envs)
+
+
+def create_game_environments(game, num_envs, seed=0, full_action_set=False):
+    """This rank's shard of a device game ('catch', 'breakout').  ``full_action_set``: under the
+    18-action head, the game's own actions in ``legal_action_masks``."""
+    from actorcritic.envs.games import DeviceGameEnvs
+    return DeviceGameEnvs(game, num_envs, num_actions=18 if full_action_set else None, seed=seed,
+                          env_offset=parallel.rank() * num_envs)
 
 
 def create_host_environments(env_fns, subprocess=True):
@@ -156,7 +174,9 @@ def save_model(checkpoint_path, model_name, step, model, optimizer):
 
 if __name__ == '__main__':
     acktr = True
-    env_id = 'BreakoutNoFrameskip-v4'
+    argv = sys.argv[1:]
+    game = argv[argv.index('--game') + 1] if '--game' in argv else None
+    env_id = 'BreakoutNoFrameskip-v4' if game is None else 'DeviceGame-' + game
     num_envs = 32
     num_steps = 20
     results_path = os.path.abspath('./results')
@@ -165,4 +185,4 @@ if __name__ == '__main__':
     os.makedirs(checkpoint_path, exist_ok=True)
     os.makedirs(summary_path, exist_ok=True)
     train_a2c_acktr(acktr, env_id, num_envs, num_steps, checkpoint_path, 'Atari-' + env_id, summary_path,
-                    mask_actions='--mask-actions' in sys.argv[1:])
+                    mask_actions='--mask-actions' in argv, game=game)

@@ -19,8 +19,8 @@ import actorcritic.envs.atari.wrappers as wrappers
 from actorcritic import checkpoint, parallel
 from actorcritic.agents import MultiEnvAgent
 from actorcritic.envs.atari.model import AtariModel
-from actorcritic.examples.atari.a2c_acktr import (create_environments, create_host_environments, load_model,
-                                                   save_model)
+from actorcritic.examples.atari.a2c_acktr import (create_environments, create_game_environments,
+                                                   create_host_environments, load_model, save_model)
 from actorcritic.multi_env import MultiEnv
 from actorcritic.nn import AdamOptimizer, ClipGlobalNormOptimizer, linear_decay
 from actorcritic.objectives import PPOObjective
@@ -29,7 +29,7 @@ from actorcritic.session import Session, get_or_create_global_step, no_op
 
 def train_ppo(env_id, num_envs, num_steps, checkpoint_path, model_name, summary_path=None, max_updates=None, seed=0,
               log_every=10, num_epochs=4, num_minibatches=4, clip_range=0.1, value_clip_range=None,
-              minibatch='envs', env_fns=None, mask_actions=False):
+              minibatch='envs', env_fns=None, mask_actions=False, game=None, on_update=None):
     """Trains an Atari model (conv3 64) with PPO.
 
     ``num_envs`` is per GPU; with WORLD_SIZE > 1 (torchrun) every rank steps its own shard.
@@ -41,9 +41,13 @@ def train_ppo(env_id, num_envs, num_steps, checkpoint_path, model_name, summary_
     makes a host env with raw RGB frames (a2c_acktr.create_host_environments); ``num_envs`` is
     then their number.
     ``mask_actions`` (``--mask-actions``): invalid-action masking, as in a2c_acktr.train_a2c_acktr.
+    ``game`` (``--game catch|breakout``), ``checkpoint_path`` None and ``on_update``: as in
+    a2c_acktr.train_a2c_acktr.
     """
     parallel.init_from_env()
-    if env_fns is not None:
+    if game is not None:
+        multi_env = MultiEnv(create_game_environments(game, num_envs, seed=seed, full_action_set=mask_actions))
+    elif env_fns is not None:
         multi_env = create_host_environments(env_fns)
         num_envs = multi_env.num_envs
     else:
@@ -69,7 +73,8 @@ def train_ppo(env_id, num_envs, num_steps, checkpoint_path, model_name, summary_
     summary_op = no_op()
 
     with Session() as session:
-        load_model(checkpoint_path, model, optimizer, global_step)
+        if checkpoint_path is not None:
+            load_model(checkpoint_path, model, optimizer, global_step)
         step = global_step.value
         updates = 0
         try:
@@ -97,11 +102,13 @@ def train_ppo(env_id, num_envs, num_steps, checkpoint_path, model_name, summary_
                     summary_writer.add(step, policy_loss=float(out[3]), baseline_loss=float(out[4]),
                                        policy_entropy=float(out[5]), approx_kl=float(out[6]),
                                        clip_fraction=float(out[7]), episode_reward=mean_episode_reward)
-                if step % 100 == 0 and step > 0 and parallel.rank() == 0:
+                if on_update is not None:
+                    on_update(updates, model)
+                if checkpoint_path is not None and step % 100 == 0 and step > 0 and parallel.rank() == 0:
                     save_model(checkpoint_path, model_name, step, model, optimizer)
         except KeyboardInterrupt:
             print('Stop requested')
-            if parallel.rank() == 0:
+            if checkpoint_path is not None and parallel.rank() == 0:
                 save_model(checkpoint_path, model_name, step, model, optimizer)
         finally:
             multi_env.close()
@@ -117,7 +124,9 @@ def create_optimizer(learning_rate):
 
 
 if __name__ == '__main__':
-    env_id = 'BreakoutNoFrameskip-v4'
+    argv = sys.argv[1:]
+    game = argv[argv.index('--game') + 1] if '--game' in argv else None
+    env_id = 'BreakoutNoFrameskip-v4' if game is None else 'DeviceGame-' + game
     num_envs = 32
     num_steps = 128
     results_path = os.path.abspath('./results')
@@ -126,4 +135,4 @@ if __name__ == '__main__':
     os.makedirs(checkpoint_path, exist_ok=True)
     os.makedirs(summary_path, exist_ok=True)
     train_ppo(env_id, num_envs, num_steps, checkpoint_path, 'Atari-' + env_id, summary_path,
-              mask_actions='--mask-actions' in sys.argv[1:])
+              mask_actions='--mask-actions' in argv, game=game)

@@ -1,7 +1,8 @@
 """Multiple environments (reference: actorcritic/multi_env.py:11-137).
 
 ``MultiEnv(envs)`` accepts either
-  * a batched device env (:class:`actorcritic.envs.atari.wrappers.SyntheticAtariEnvs`):
+  * a batched device env (:class:`actorcritic.envs.atari.wrappers.SyntheticAtariEnvs`, or
+    the games of :class:`actorcritic.envs.games.DeviceGameEnvs`, recognised by ``step_into``):
     the hot path — one kernel steps every env, observations never leave HBM; or
   * a batched adaptor over host envs that return raw frames
     (:class:`actorcritic.envs.atari.wrappers.HostAtariEnvs`, marked ``host_stepped``):

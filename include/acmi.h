@@ -557,6 +557,42 @@ int acmi_env_step(const acmi_env_state_t* st, int N, int env_offset,
                   int64_t ld, acmi_stream_t stream);
 
 /* ------------------------------------------------------------------------
+ * Device games: small real games that step and render on the
+ * GPU straight into the stacked observation -- game 0 Catch (3 own actions),
+ * game 1 Breakout (4).  Integer dynamics; the rule book is the host
+ * implementation actorcritic/envs/games/host.py (HostGame), which the kernel
+ * reproduces bit for bit: frames, rewards, terminals, state.  Actions at or
+ * past a game's own count act as NOOP.
+ * acmi_game_step has acmi_env_step's arguments and semantics word for word
+ * (lazy auto-reset at the step after a terminal, the FrameStackWrapper roll
+ * with zero-fill on a terminal step and the reset frame repeated 4x,
+ * episode_rewards NaN unless the episode ended; in place allowed); strides
+ * are multiples of 16, at least 84*84*4.  vars holds acmi_game_state_ints()
+ * int32 per env: ball x, y, vx, vy, paddle x, lives, three brick words (row r,
+ * column c: bit 12*(r%2)+c of word r/2), zero padding.  The struct's size
+ * is not among acmi_abi_struct_sizes' five: acmi_game_state_bytes() is it.
+ * ---------------------------------------------------------------------- */
+typedef struct acmi_game_state {
+  int32_t* episode;   /* episode index                                    */
+  int32_t* step;      /* steps taken in the current episode               */
+  float* total;       /* EpisodeInfoWrapper.total_reward                   */
+  uint8_t* done;      /* _AutoResetWrapper._terminated                     */
+  int32_t* vars;      /* [N][acmi_game_state_ints()] game variables        */
+  int32_t game;       /* 0 Catch, 1 Breakout                               */
+} acmi_game_state_t;
+
+int acmi_game_state_ints(void);
+int64_t acmi_game_state_bytes(void);
+int acmi_game_reset(const acmi_game_state_t* st, int N, int env_offset,
+                    uint32_t seed, uint8_t* obs_out, int64_t out_stride,
+                    acmi_stream_t stream);
+int acmi_game_step(const acmi_game_state_t* st, int N, int env_offset,
+                   uint32_t seed, const int32_t* actions, const uint8_t* obs_in,
+                   int64_t in_stride, uint8_t* obs_out, int64_t out_stride,
+                   float* rewards, uint8_t* terminals, float* episode_rewards,
+                   int64_t ld, acmi_stream_t stream);
+
+/* ------------------------------------------------------------------------
  * Atari frame preprocessing for real (raw RGB) frames, batched over envs:
  * replaces the frame half of the reference's per-env wrapper chain
  *   AtariFrameskipWrapper  (envs/atari/wrappers.py:54-67: np.amax of the last

@@ -1,0 +1,88 @@
+#!/usr/bin/env python
+"""Learning curves on the device games.  Needs a GPU.
+
+Trains A2C, ACKTR or PPO (the examples' settings) on Catch or Breakout from a seed and,
+every --every updates, plays a separate batch of envs with the greedy policy
+(envs.games.evaluate): one JSON line per point with the env-steps so far and the mean
+return, after a first line with the uniform policy's.  The lines also go to --out.
+
+    python scripts/learn_games.py --algo a2c --game catch --updates 2000 --every 250 --seeds 1 2 3
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, 'actor-critic_amd'))
+
+
+def run(args, seed, emit):
+    import torch
+    assert torch.cuda.is_available(), 'no GPU: nothing is learned without one'
+    from actorcritic import session as sess
+    from actorcritic.envs.games import DeviceGameEnvs, evaluate
+    from actorcritic.examples.atari.a2c_acktr import train_a2c_acktr
+    from actorcritic.examples.atari.ppo import train_ppo
+    torch.cuda.set_device(0)
+    sess.reset_default_graph()
+    N, T, E = args.envs, args.steps, args.episodes
+    head = dict(algo=args.algo, game=args.game, seed=seed, envs=N, steps=T, eval_envs=args.eval_envs, eval_episodes=E)
+
+    def stats(returns):
+        r = returns.double().flatten()
+        return dict(mean_return=round(float(r.mean()), 4), var=round(float(r.var(unbiased=True)), 4), n=r.numel())
+
+    eval_envs = lambda: DeviceGameEnvs(args.game, args.eval_envs, seed=1000 + seed)
+    emit(dict(head, policy='uniform', updates=0, env_steps=0, **stats(evaluate(None, eval_envs(), E, uniform=True,
+                                                                                 seed=seed))))
+    t0 = time.perf_counter()
+
+    def on_update(updates, model):
+        if updates % args.every == 0 or updates == args.updates:
+            torch.cuda.synchronize()
+            train_s = time.perf_counter() - t0
+            emit(dict(head, policy='sampled' if args.sample else 'greedy', updates=updates,
+                      env_steps=updates * N * T, wall_s=round(train_s, 2),
+                      **stats(evaluate(model, eval_envs(), E, greedy=not args.sample, seed=seed))))
+
+    if args.algo == 'ppo':
+        train_ppo(args.game, N, T, None, args.game, max_updates=args.updates, seed=seed, game=args.game,
+                  on_update=on_update)
+    else:
+        train_a2c_acktr(args.algo == 'acktr', args.game, N, T, None, args.game, max_updates=args.updates, seed=seed,
+                        game=args.game, on_update=on_update)
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument('--algo', choices=('a2c', 'acktr', 'ppo'), default='a2c')
+    ap.add_argument('--game', choices=('catch', 'breakout'), default='catch')
+    ap.add_argument('--envs', type=int, default=32)
+    ap.add_argument('--steps', type=int, default=None, help='rollout length (default: a2c 5, acktr 20, ppo 128)')
+    ap.add_argument('--updates', type=int, default=2000)
+    ap.add_argument('--every', type=int, default=250)
+    ap.add_argument('--seeds', type=int, nargs='+', default=[1])
+    ap.add_argument('--eval-envs', type=int, default=32)
+    ap.add_argument('--episodes', type=int, default=8, help='evaluation episodes per env')
+    ap.add_argument('--sample', action='store_true', help='evaluate draws from the policy instead of its mode')
+    ap.add_argument('--out', default=None, help='also append the JSON lines to this file')
+    args = ap.parse_args()
+    if args.steps is None:
+        args.steps = {'a2c': 5, 'acktr': 20, 'ppo': 128}[args.algo]  # the examples' rollout lengths
+    out = open(args.out, 'a') if args.out else None
+
+    def emit(rec):
+        line = json.dumps(rec)
+        print(line, flush=True)
+        if out is not None:
+            out.write(line + '\n')
+            out.flush()
+
+    for seed in args.seeds:
+        run(args, seed, emit)
+
+
+if __name__ == '__main__':
+    main()
