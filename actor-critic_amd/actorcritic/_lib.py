@@ -53,6 +53,11 @@ class GameState(ctypes.Structure):
                 ('game', ctypes.c_int32)]
 
 
+class GameRules(ctypes.Structure):
+    # acmi_game_rules_t: acmi_game_step_cuts (max_steps 0 = the game's own cap)
+    _fields_ = [('episodic_life', ctypes.c_int32), ('max_steps', ctypes.c_int32)]
+
+
 class RolloutIO(ctypes.Structure):
     _fields_ = [('seed', c_u32), ('stream_id', c_u32), ('counter', c_u32), ('counter_dev', c_vp),
                 ('row_offset', c_int), ('actions', c_vp), ('bad_rows', c_vp), ('state', EnvState),
@@ -110,6 +115,9 @@ _SIGS = {
                                          ctypes.POINTER(RolloutIO), c_vp, c_vp]),
     'acmi_returns': (c_int, [c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp]),
     'acmi_gae': (c_int, [c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_float, c_float, c_vp, c_vp, c_vp]),
+    # the same + truncated [N][T] u8 after terminals
+    'acmi_returns_trunc': (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    'acmi_gae_trunc': (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_float, c_float, c_vp, c_vp, c_vp]),
     'acmi_adv_moments_ws_doubles': (c_i64, [c_i64]),
     'acmi_adv_moments': (c_int, [c_vp, c_i64, c_vp, c_vp, c_vp]),
     'acmi_adv_normalize': (c_int, [c_vp, c_i64, c_vp, ctypes.c_double, ctypes.c_double, c_vp]),
@@ -159,6 +167,9 @@ _SIGS = {
     'acmi_game_reset': (c_int, [ctypes.POINTER(GameState), c_int, c_int, c_u32, c_vp, c_i64, c_vp]),
     'acmi_game_step': (c_int, [ctypes.POINTER(GameState), c_int, c_int, c_u32, c_vp, c_vp, c_i64, c_vp, c_i64,
                                c_vp, c_vp, c_vp, c_i64, c_vp]),
+    # acmi_game_step + rules and truncated (nullable) ahead of episode_rewards
+    'acmi_game_step_cuts': (c_int, [ctypes.POINTER(GameState), ctypes.POINTER(GameRules), c_int, c_int, c_u32, c_vp,
+                                    c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
     'acmi_atari_preprocess': (c_int, [c_vp, c_i64, c_i64, c_vp, c_int, c_int, c_int, c_vp, c_i64, c_vp]),
     'acmi_atari_stack': (c_int, [c_vp, c_i64, c_i64, c_vp, c_int, c_int, c_int, c_vp, c_int, c_vp, c_vp,
                                  c_i64, c_vp]),

@@ -79,6 +79,10 @@ class _RolloutBuffers(object):
         self.rewards = torch.zeros((N, T), dtype=torch.float32, device=dev)
         self.terminals = torch.zeros((N, T), dtype=torch.uint8, device=dev)
         self.episode_rewards = torch.zeros((N, T), dtype=torch.float32, device=dev)
+        # terminals the step cap alone caused (the targets keep their bootstrap): filled by
+        # envs that say ``emits_truncations`` (envs.games.DeviceGameEnvs with an option on)
+        self.truncations = torch.zeros((N, T), dtype=torch.uint8, device=dev)
+        self.emits_truncations = bool(getattr(env, 'emits_truncations', False))
         self.acts = engine.activations(N * T, 'rollout')
         self.bad_host = torch.zeros(2, dtype=torch.int32, pin_memory=True)  # (engine._bad_counts)
         self.bad_event = None
@@ -133,6 +137,9 @@ class MultiEnvAgent(Agent):
         self._bufs = None
         self._copy = bool(copy_batches)
         self._mask_actions = bool(mask_actions)
+        # the last rollout's truncations, [N, T] bool on the device (the feed of
+        # model.truncations_placeholder); None for envs that emit none
+        self.last_truncations = None
         if self._mask_actions:
             masks = getattr(getattr(multi_env, 'batched', None), 'legal_action_masks', None)
             if masks is None:
@@ -281,7 +288,7 @@ class MultiEnvAgent(Agent):
                 else:
                     dst, dstride = rb.next_obs.data_ptr(), OBS_BYTES
                 env.step_into(act_t.data_ptr(), src, T * OBS_BYTES, dst, dstride, rew0 + 4 * t, term0 + t,
-                              ep0 + 4 * t, T)
+                              ep0 + 4 * t, T, **_trunc_arg(rb, t))
             rb.actions.copy_(rb.actions_tn.t())
         rb.bad_host.copy_(eng._bad_counts, non_blocking=True)
         rb.bad_event = torch.cuda.Event()
@@ -347,13 +354,22 @@ class MultiEnvAgent(Agent):
         from actorcritic.envs.atari.wrappers import EpisodeInfoBatch
         self._observations = rb.next_obs
         out = (rb.obs, rb.actions, rb.rewards, rb.terminals.view(torch.bool), rb.next_obs, rb.episode_rewards)
+        trunc = rb.truncations.view(torch.bool) if rb.emits_truncations else None
         if self._copy:
             out = tuple(x.clone() for x in out)
+            trunc = None if trunc is None else trunc.clone()
+        self.last_truncations = trunc
         obs = out[0]
         # the update re-uses the rollout activations for exactly these observations
         fwd = ForwardOut(eng, rb.acts, N, T, obs.view(N * T, 84, 84, 4))
         eng.register_rollout(obs, fwd)
         return out[:5] + (EpisodeInfoBatch(out[5]),)
+
+
+def _trunc_arg(rb, row):
+    """step_into's keyword for the truncation byte of batch element ``row`` (the
+    terminals' layout), for envs that emit truncations; none otherwise."""
+    return {'trunc_ptr': rb.truncations.data_ptr() + row} if rb.emits_truncations else {}
 
 
 def _mask_rows(eng, N):
@@ -414,16 +430,17 @@ def _half_step(eng, env, rb, h, N2, T, A, t, seed, dev_ctr=False, fuse=False):
                       ctypes.byref(acts), T, ctypes.byref(io), eng.stream())
         return
     eng.forward(src, N2, acts, want_value=True, img_stride=T * OBS_BYTES, act_stride=T)
+    trunc = _trunc_arg(rb, row)
     if legal is not None:
         _lib.call('acmi_sample_actions_masked', _lib.c_vp(rb.acts.logits.data_ptr() + 4 * row * A), T * A, N2, A,
                   seed, 0, ctr_dev, ctr, row0, None, 0, _lib.c_vp(legal), _lib.c_vp(act_t),
                   _lib.c_vp(eng._bad_rows.data_ptr()), eng.stream())
-        env.step_range_into(n0, N2, act_t, src, T * OBS_BYTES, dst, dstride, rew, term, ep, T)
+        env.step_range_into(n0, N2, act_t, src, T * OBS_BYTES, dst, dstride, rew, term, ep, T, **trunc)
         return
     _lib.call('acmi_sample_actions_dev', _lib.c_vp(rb.acts.logits.data_ptr() + 4 * row * A), T * A, N2, A,
               seed, 0, ctr_dev, ctr, row0, None, 0, _lib.c_vp(act_t),
               _lib.c_vp(eng._bad_rows.data_ptr()), eng.stream())
-    env.step_range_into(n0, N2, act_t, src, T * OBS_BYTES, dst, dstride, rew, term, ep, T)
+    env.step_range_into(n0, N2, act_t, src, T * OBS_BYTES, dst, dstride, rew, term, ep, T, **trunc)
 
 
 def transpose_list(values):

@@ -19,7 +19,8 @@ import torch
 from actorcritic import _lib, spaces
 from actorcritic._engine import OBS_BYTES
 from actorcritic.envs.atari.wrappers import EpisodeInfoBatch, _mask_tensor, action_mask_bits
-from actorcritic.envs.games.host import GAME_ACTIONS, GAMES, STATE_INTS, HostGame, game_id
+from actorcritic.envs.games.host import (GAME_ACTIONS, GAMES, STATE_INTS, HostGame, check_max_episode_steps,
+                                         game_id)
 
 __all__ = ['DeviceGameEnvs', 'HostGame', 'evaluate', 'GAMES', 'GAME_ACTIONS']
 
@@ -38,14 +39,30 @@ class DeviceGameEnvs(object):
             set as one word per env (``MultiEnvAgent(mask_actions=True)``).
         seed: game seed (an episode's start is a pure function of seed, env, episode).
         env_offset: global id of the first env (data-parallel shards use rank*num_envs).
+        episodic_life: a lost life is a terminal for the learner; the game goes on in place
+            and resets only when it is really over (host.py, "Cuts").
+        max_episode_steps: step cap, 1..2000 (either game); None: the game's own (Breakout
+            2000, Catch none).  A terminal that the cap alone caused is a truncation.
+
+    With either option set the envs step through ``acmi_game_step_cuts`` and
+    ``emits_truncations`` is True: ``step_into(..., trunc_ptr=)`` writes one truncation byte
+    per env beside the terminals (the rollout: ``MultiEnvAgent.last_truncations``), and the
+    batched ``step()`` leaves them in ``last_truncations`` ([N] bool device tensor; None for
+    envs that emit none).  ``episode_rewards`` stay whole-game totals, at a game over only.
     """
 
     # acmi_rollout_step's tail hard-wires the synthetic stepper: the rollout steps
     # these envs unfused (forward + sampler + step_into), see agents._RolloutBuffers
     fused_step = False
 
-    def __init__(self, game, num_envs, num_actions=None, seed=0, env_offset=0, device=None):
+    def __init__(self, game, num_envs, num_actions=None, seed=0, env_offset=0, device=None, episodic_life=False,
+                 max_episode_steps=None):
         _lib.require_gpu()
+        self.episodic_life = bool(episodic_life)
+        self.max_episode_steps = check_max_episode_steps(max_episode_steps)
+        self.emits_truncations = self.episodic_life or self.max_episode_steps is not None
+        self._rules = _lib.GameRules(int(self.episodic_life), self.max_episode_steps or 0)
+        self.last_truncations = None
         self.game_id = game_id(game)
         self.game = GAMES[self.game_id]
         self.num_own_actions = GAME_ACTIONS[self.game]
@@ -97,15 +114,26 @@ class DeviceGameEnvs(object):
         _lib.call('acmi_game_reset', ctypes.byref(self.state), self.num_envs, self.env_offset, self.seed,
                   ctypes.c_void_p(obs_ptr), stride, self._stream())
 
-    def step_into(self, actions_ptr, obs_in_ptr, in_stride, obs_out_ptr, out_stride, rew_ptr, term_ptr, ep_ptr, ld):
+    def step_into(self, actions_ptr, obs_in_ptr, in_stride, obs_out_ptr, out_stride, rew_ptr, term_ptr, ep_ptr, ld,
+                  trunc_ptr=None):
         self.step_range_into(0, self.num_envs, actions_ptr, obs_in_ptr, in_stride, obs_out_ptr, out_stride, rew_ptr,
-                             term_ptr, ep_ptr, ld)
+                             term_ptr, ep_ptr, ld, trunc_ptr)
 
     def step_range_into(self, n0, n, actions_ptr, obs_in_ptr, in_stride, obs_out_ptr, out_stride, rew_ptr,
-                        term_ptr, ep_ptr, ld):
-        """step_into for envs n0 .. n0+n-1 only (every pointer already at env n0)."""
+                        term_ptr, ep_ptr, ld, trunc_ptr=None):
+        """step_into for envs n0 .. n0+n-1 only (every pointer already at env n0).
+        trunc_ptr: u8 truncations, laid out as the terminals (envs with ``emits_truncations``)."""
         if not (0 <= n0 and 0 <= n and n0 + n <= self.num_envs):
             raise ValueError('envs {} .. {} outside the batch of {}'.format(n0, n0 + n - 1, self.num_envs))
+        if self.emits_truncations:
+            _lib.call('acmi_game_step_cuts', ctypes.byref(self.range_state(n0)), ctypes.byref(self._rules), n,
+                      self.env_offset + n0, self.seed, ctypes.c_void_p(actions_ptr), ctypes.c_void_p(obs_in_ptr),
+                      in_stride, ctypes.c_void_p(obs_out_ptr), out_stride, ctypes.c_void_p(rew_ptr),
+                      ctypes.c_void_p(term_ptr), ctypes.c_void_p(trunc_ptr), ctypes.c_void_p(ep_ptr), ld,
+                      self._stream())
+            return
+        if trunc_ptr is not None:
+            raise ValueError('these envs emit no truncations (episodic_life / max_episode_steps are off)')
         _lib.call('acmi_game_step', ctypes.byref(self.range_state(n0)), n, self.env_offset + n0, self.seed,
                   ctypes.c_void_p(actions_ptr), ctypes.c_void_p(obs_in_ptr), in_stride, ctypes.c_void_p(obs_out_ptr),
                   out_stride, ctypes.c_void_p(rew_ptr), ctypes.c_void_p(term_ptr), ctypes.c_void_p(ep_ptr), ld,
@@ -117,15 +145,19 @@ class DeviceGameEnvs(object):
         return self._obs.clone()
 
     def step(self, actions):
-        """actions: [N] ints -> (obs [N,84,84,4] u8, rewards [N], terminals [N] bool, EpisodeInfoBatch)."""
+        """actions: [N] ints -> (obs [N,84,84,4] u8, rewards [N], terminals [N] bool, EpisodeInfoBatch);
+        the step's truncations ([N] bool) are left in ``last_truncations`` (class docstring)."""
         a = actions if isinstance(actions, torch.Tensor) else torch.as_tensor(np.asarray(actions))
         a = a.to(device=self.device, dtype=torch.int32).contiguous()
         N = self.num_envs
         rew = torch.empty(N, dtype=torch.float32, device=self.device)
         term = torch.empty(N, dtype=torch.uint8, device=self.device)
         ep = torch.empty(N, dtype=torch.float32, device=self.device)
+        trunc = torch.empty(N, dtype=torch.uint8, device=self.device) if self.emits_truncations else None
         self.step_into(a.data_ptr(), self._obs.data_ptr(), OBS_BYTES, self._obs.data_ptr(), OBS_BYTES,
-                       rew.data_ptr(), term.data_ptr(), ep.data_ptr(), 1)
+                       rew.data_ptr(), term.data_ptr(), ep.data_ptr(), 1,
+                       trunc_ptr=None if trunc is None else trunc.data_ptr())
+        self.last_truncations = None if trunc is None else trunc.view(torch.bool)
         return self._obs.clone(), rew, term.view(torch.bool), EpisodeInfoBatch(ep[:, None])
 
     def close(self):
@@ -149,7 +181,14 @@ def evaluate(model, envs, episodes_per_env, greedy=True, seed=0, uniform=False, 
     return_actions: also returns the actions taken, int32 [steps, num_envs].
     max_steps: give up (RuntimeError) after that many steps; default
         episodes_per_env * 2001 (Breakout's step cap + the reset step).
+
+    ``envs`` with ``episodic_life=True`` raise ValueError: the episode count here is a count
+    of terminals, and a life cut is not the end of a game.  (``max_episode_steps`` is fine:
+    a truncated game is over and reports its total.)
     """
+    if getattr(envs, 'episodic_life', False):
+        raise ValueError('evaluate() counts terminals as finished games: build the evaluation envs without '
+                         'episodic_life')
     N, E = envs.num_envs, int(episodes_per_env)
     if E < 1:
         raise ValueError('episodes_per_env must be at least 1')

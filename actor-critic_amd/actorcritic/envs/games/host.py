@@ -42,6 +42,34 @@ Breakout (own actions 0 NOOP, 1 FIRE = NOOP, 2 RIGHT, 3 LEFT):
 
 Actions at or past a game's own count act as NOOP.  The ball is drawn over the paddle,
 the paddle over the bricks.
+
+Cuts (``HostGame(..., episodic_life=False, max_episode_steps=None)``; the stepper's
+``acmi_game_step_cuts``).  The flag that tells the learner "cut the return here" is not
+the flag that says "the game restarts", and a cut may or may not keep its bootstrap:
+
+    cap        = max_episode_steps (1..2000, either game), else the game's own
+                 (Breakout 2000, Catch none);
+    life_lost  = lives decreased in this step;
+    game_over  = the game's own end (Catch: by == 76; Breakout: lives == 0 or no brick
+                 left) or steps >= cap;
+    terminal   = game_over or (episodic_life and life_lost);
+    truncated  = steps >= cap and the game's own end has not fired and not
+                 (episodic_life and life_lost): the cap alone ended the episode, and the
+                 learner should still bootstrap from the value of the next observation.
+
+With an option on, step()'s info is {'truncated': bool, 'game_over': bool}; with none it
+stays {} and everything is as before.  reset() after a terminal that was not game_over
+CONTINUES IN PLACE: the state, ``steps`` and ``episode`` are untouched and it returns
+render() of the respawned ball (a frame stack above it restarts from that frame).  This
+is deliberately not the NOOP step of the reference's AtariEpisodicLifeWrapper
+(envs/atari/wrappers.py:89-117), and the whole contract rests on it: under the same
+actions an ``episodic_life=True`` game produces exactly the frames, rewards and state
+vectors of the plain game; only ``terminal`` differs, and what the wrappers above do with
+it.  Catch has one life, so ``episodic_life`` changes nothing there.  The device stepper
+has EpisodeInfoWrapper inside the life cut, as the reference chain does: its episode
+totals are whole-game totals at a game over.  (An EpisodeInfoWrapper put around an
+``episodic_life=True`` HostGame on the list path sees that game's terminals and so totals
+per life.)
 """
 
 import numpy as np
@@ -84,13 +112,31 @@ def game_id(game):
     raise ValueError('unknown game {!r}: one of {}'.format(game, GAMES))
 
 
+def check_max_episode_steps(max_episode_steps):
+    """None (the game's own cap) or an int in 1..2000; ValueError otherwise."""
+    if max_episode_steps is None:
+        return None
+    if isinstance(max_episode_steps, bool) or not isinstance(max_episode_steps, (int, np.integer)) or \
+            not 1 <= int(max_episode_steps) <= BREAKOUT_MAX_STEPS:
+        raise ValueError('max_episode_steps must be None or an int in 1..{}, got {!r}'.format(
+            BREAKOUT_MAX_STEPS, max_episode_steps))
+    return int(max_episode_steps)
+
+
 class HostGame(object):
     """One game on the host.  reset() -> frame [84, 84, 1] u8; step(a) -> (frame, reward,
     terminal, info).  Every reset() starts the next episode (0, 1, ...), as the device
-    stepper's lazy auto-reset does."""
+    stepper's lazy auto-reset does -- except after a life-loss terminal under
+    ``episodic_life``, where the game continues in place (module docstring, "Cuts")."""
 
-    def __init__(self, game, seed=0, env_id=0):
+    def __init__(self, game, seed=0, env_id=0, episodic_life=False, max_episode_steps=None):
         self.game = GAMES[game_id(game)]
+        self.episodic_life = bool(episodic_life)
+        self.max_episode_steps = check_max_episode_steps(max_episode_steps)
+        self._cap = self.max_episode_steps
+        if self._cap is None and self.game == 'breakout':
+            self._cap = BREAKOUT_MAX_STEPS
+        self._continue = False  # the last terminal was not a game over: reset() continues in place
         self.seed = int(seed) & _M32
         self.env_id = int(env_id)
         self.num_own_actions = GAME_ACTIONS[self.game]
@@ -127,6 +173,9 @@ class HostGame(object):
 
     # -- gym-like API --------------------------------------------------------------
     def reset(self):
+        if self._continue:
+            self._continue = False
+            return self.render()
         self.episode += 1
         self.steps = 0
         self.px = 36
@@ -144,8 +193,17 @@ class HostGame(object):
         if not 0 <= a < self.num_own_actions:
             a = 0
         self.steps += 1
-        reward, terminal = self._catch(a) if self.game == 'catch' else self._breakout(a)
-        return self.render(), float(reward), bool(terminal), {}
+        lives = self.lives
+        reward, own = self._catch(a) if self.game == 'catch' else self._breakout(a)
+        capped = self._cap is not None and self.steps >= self._cap
+        game_over = own or capped
+        life_cut = self.episodic_life and self.lives < lives
+        terminal = game_over or life_cut
+        self._continue = terminal and not game_over
+        info = {}
+        if self.episodic_life or self.max_episode_steps is not None:
+            info = {'truncated': bool(capped and not own and not life_cut), 'game_over': bool(game_over)}
+        return self.render(), float(reward), bool(terminal), info
 
     def _catch(self, a):
         if a == 1:
@@ -188,8 +246,7 @@ class HostGame(object):
             self.lives -= 1
             if self.lives > 0:
                 self._spawn_ball()
-        terminal = self.lives == 0 or not any(self.bricks) or self.steps >= BREAKOUT_MAX_STEPS
-        return reward, terminal
+        return reward, self.lives == 0 or not any(self.bricks)  # (the step cap: step())
 
     def render(self):
         f = np.zeros((84, 84, 1), np.uint8)

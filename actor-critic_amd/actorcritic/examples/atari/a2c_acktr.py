@@ -24,7 +24,7 @@ from actorcritic.session import Session, get_or_create_global_step, no_op
 
 def train_a2c_acktr(acktr, env_id, num_envs, num_steps, checkpoint_path, model_name, summary_path=None,
                     max_updates=None, seed=0, log_every=10, env_fns=None, mask_actions=False, game=None,
-                    on_update=None):
+                    on_update=None, episodic_life=False, max_episode_steps=None):
     """Trains an Atari model with A2C (RMSProp, conv3 64) or ACKTR (K-FAC, conv3 32).
 
     ``num_envs`` is per GPU; with WORLD_SIZE > 1 (torchrun) every rank steps its own shard.
@@ -36,12 +36,20 @@ def train_a2c_acktr(acktr, env_id, num_envs, num_steps, checkpoint_path, model_n
     ``legal_action_masks``); actions, losses and K-FAC statistics then run over the legal set.
     ``game`` (``--game catch|breakout``): a device game (envs.games.DeviceGameEnvs) instead of the
     synthetic stepper -- something that can be learned; ``env_id`` then only names the results.
+    ``episodic_life`` (``--episodic-life``) and ``max_episode_steps`` (``--max-episode-steps N``), device
+    games only: a lost life is a terminal for the learner, and a step cap of N (1..2000) whose terminals
+    are truncations -- the targets keep their bootstrap there (``model.truncations_placeholder``).
+    Evaluation envs are built without episodic life (envs.games.evaluate counts terminals as games).
     ``checkpoint_path`` None: nothing is loaded or saved.  ``on_update(updates, model)`` is called
     after every update (learning curves: scripts/learn_games.py).
     """
     parallel.init_from_env()
+    if game is None and (episodic_life or max_episode_steps is not None):
+        raise ValueError('episodic_life and max_episode_steps need a device game (game=)')
     if game is not None:
-        multi_env = MultiEnv(create_game_environments(game, num_envs, seed=seed, full_action_set=mask_actions))
+        multi_env = MultiEnv(create_game_environments(game, num_envs, seed=seed, full_action_set=mask_actions,
+                                                      episodic_life=episodic_life,
+                                                      max_episode_steps=max_episode_steps))
     elif env_fns is not None:
         multi_env = create_host_environments(env_fns)
         num_envs = multi_env.num_envs
@@ -81,13 +89,16 @@ def train_a2c_acktr(acktr, env_id, num_envs, num_steps, checkpoint_path, model_n
                 fetches = [summary_op, global_step, optimize_op]
                 if summary_writer is not None and step % log_every == 0:
                     fetches += [objective.policy_loss, objective.baseline_loss, objective.mean_entropy]
-                out = session.run(fetches, feed_dict={
+                feed_dict = {
                     model.observations_placeholder: observations,
                     model.bootstrap_observations_placeholder: next_observations,
                     model.actions_placeholder: actions,
                     model.rewards_placeholder: rewards,
                     model.terminals_placeholder: terminals,
-                }, host=len(fetches) > 3)
+                }
+                if agent.last_truncations is not None:  # time limits keep their bootstrap (objectives.py)
+                    feed_dict[model.truncations_placeholder] = agent.last_truncations
+                out = session.run(fetches, feed_dict=feed_dict, host=len(fetches) > 3)
                 step = global_step.value
                 updates += 1
                 if len(out) > 3:
@@ -121,12 +132,15 @@ def create_environments(env_id, num_envs, seed=0, full_action_set=False):
                                        env_offset=parallel.rank() * num_envs)
 
 
-def create_game_environments(game, num_envs, seed=0, full_action_set=False):
+def create_game_environments(game, num_envs, seed=0, full_action_set=False, episodic_life=False,
+                             max_episode_steps=None):
     """This rank's shard of a device game ('catch', 'breakout').  ``full_action_set``: under the
-    18-action head, the game's own actions in ``legal_action_masks``."""
+    18-action head, the game's own actions in ``legal_action_masks``.  ``episodic_life`` and
+    ``max_episode_steps``: DeviceGameEnvs' (training envs only: evaluate() refuses episodic life)."""
     from actorcritic.envs.games import DeviceGameEnvs
     return DeviceGameEnvs(game, num_envs, num_actions=18 if full_action_set else None, seed=seed,
-                          env_offset=parallel.rank() * num_envs)
+                          env_offset=parallel.rank() * num_envs, episodic_life=episodic_life,
+                          max_episode_steps=max_episode_steps)
 
 
 def create_host_environments(env_fns, subprocess=True):
@@ -185,4 +199,6 @@ if __name__ == '__main__':
     os.makedirs(checkpoint_path, exist_ok=True)
     os.makedirs(summary_path, exist_ok=True)
     train_a2c_acktr(acktr, env_id, num_envs, num_steps, checkpoint_path, 'Atari-' + env_id, summary_path,
-                    mask_actions='--mask-actions' in argv, game=game)
+                    mask_actions='--mask-actions' in argv, game=game, episodic_life='--episodic-life' in argv,
+                    max_episode_steps=(int(argv[argv.index('--max-episode-steps') + 1])
+                                       if '--max-episode-steps' in argv else None))

@@ -29,7 +29,8 @@ from actorcritic.session import Session, get_or_create_global_step, no_op
 
 def train_ppo(env_id, num_envs, num_steps, checkpoint_path, model_name, summary_path=None, max_updates=None, seed=0,
               log_every=10, num_epochs=4, num_minibatches=4, clip_range=0.1, value_clip_range=None,
-              minibatch='envs', env_fns=None, mask_actions=False, game=None, on_update=None):
+              minibatch='envs', env_fns=None, mask_actions=False, game=None, on_update=None, episodic_life=False,
+              max_episode_steps=None):
     """Trains an Atari model (conv3 64) with PPO.
 
     ``num_envs`` is per GPU; with WORLD_SIZE > 1 (torchrun) every rank steps its own shard.
@@ -41,12 +42,17 @@ def train_ppo(env_id, num_envs, num_steps, checkpoint_path, model_name, summary_
     makes a host env with raw RGB frames (a2c_acktr.create_host_environments); ``num_envs`` is
     then their number.
     ``mask_actions`` (``--mask-actions``): invalid-action masking, as in a2c_acktr.train_a2c_acktr.
-    ``game`` (``--game catch|breakout``), ``checkpoint_path`` None and ``on_update``: as in
+    ``game`` (``--game catch|breakout``), ``episodic_life`` (``--episodic-life``), ``max_episode_steps``
+    (``--max-episode-steps N``), ``checkpoint_path`` None and ``on_update``: as in
     a2c_acktr.train_a2c_acktr.
     """
     parallel.init_from_env()
+    if game is None and (episodic_life or max_episode_steps is not None):
+        raise ValueError('episodic_life and max_episode_steps need a device game (game=)')
     if game is not None:
-        multi_env = MultiEnv(create_game_environments(game, num_envs, seed=seed, full_action_set=mask_actions))
+        multi_env = MultiEnv(create_game_environments(game, num_envs, seed=seed, full_action_set=mask_actions,
+                                                      episodic_life=episodic_life,
+                                                      max_episode_steps=max_episode_steps))
     elif env_fns is not None:
         multi_env = create_host_environments(env_fns)
         num_envs = multi_env.num_envs
@@ -87,13 +93,16 @@ def train_ppo(env_id, num_envs, num_steps, checkpoint_path, model_name, summary_
                 if summary_writer is not None and step % log_every == 0:
                     fetches += [objective.policy_loss, objective.baseline_loss, objective.mean_entropy,
                                 objective.approx_kl, objective.clip_fraction]
-                out = session.run(fetches, feed_dict={
+                feed_dict = {
                     model.observations_placeholder: observations,
                     model.bootstrap_observations_placeholder: next_observations,
                     model.actions_placeholder: actions,
                     model.rewards_placeholder: rewards,
                     model.terminals_placeholder: terminals,
-                }, host=len(fetches) > 3)
+                }
+                if agent.last_truncations is not None:  # time limits keep their bootstrap (objectives.py)
+                    feed_dict[model.truncations_placeholder] = agent.last_truncations
+                out = session.run(fetches, feed_dict=feed_dict, host=len(fetches) > 3)
                 step = global_step.value
                 updates += 1
                 if len(out) > 3:
@@ -135,4 +144,6 @@ if __name__ == '__main__':
     os.makedirs(checkpoint_path, exist_ok=True)
     os.makedirs(summary_path, exist_ok=True)
     train_ppo(env_id, num_envs, num_steps, checkpoint_path, 'Atari-' + env_id, summary_path,
-              mask_actions='--mask-actions' in argv, game=game)
+              mask_actions='--mask-actions' in argv, game=game, episodic_life='--episodic-life' in argv,
+              max_episode_steps=(int(argv[argv.index('--max-episode-steps') + 1])
+                                 if '--max-episode-steps' in argv else None))

@@ -23,6 +23,7 @@ class ActorCriticModel(object, metaclass=ABCMeta):
         self._actions_placeholder = None
         self._rewards_placeholder = None
         self._terminals_placeholder = None
+        self._truncations_placeholder = None
 
         self._setup_placeholders(observation_space, action_space)
 
@@ -51,6 +52,14 @@ class ActorCriticModel(object, metaclass=ABCMeta):
         return self._terminals_placeholder
 
     @property
+    def truncations_placeholder(self):
+        """Optional, beyond the reference's five: bool [env, step], set where a terminal is
+        a time-limit truncation.  Fed, the objectives' targets keep the bootstrap from the
+        next observation's value at those steps (acmi_returns_trunc / acmi_gae_trunc);
+        unfed, every terminal cuts it, as in the reference."""
+        return self._truncations_placeholder
+
+    @property
     def policy(self):
         return self._policy
 
@@ -69,6 +78,7 @@ class ActorCriticModel(object, metaclass=ABCMeta):
         self._actions_placeholder = _space_placeholder(action_space, [None, None], 'actions')
         self._rewards_placeholder = Placeholder(np.float32, [None, None], 'rewards')
         self._terminals_placeholder = Placeholder(np.bool_, [None, None], 'terminals')
+        self._truncations_placeholder = Placeholder(np.bool_, [None, None], 'truncations')
 
     def register_layers(self, layer_collection):
         raise NotImplementedError()

@@ -16,6 +16,12 @@ the policy loss, acmi_adv_moments / acmi_adv_normalize; under data parallelism
 the moments are summed over ranks, so every rank normalises with the global
 batch's mean and std).
 
+Time limits (beyond the reference as well): when ``model.truncations_placeholder`` is
+fed (bool [env, step]: the terminals that a step cap alone caused, ``MultiEnvAgent.
+last_truncations``), those terminals still cut the return but keep the bootstrap from
+the value of the next observation -- row t+1 of the batch, or the bootstrap row at
+t = T-1 -- through acmi_returns_trunc / acmi_gae_trunc.  Unfed, every terminal cuts it.
+
 :class:`PPOObjective` (also beyond the reference) shares those targets and
 advantages and replaces the loss by PPO's clipped surrogate (acmi_ppo_loss); its
 ``optimize_shared`` op takes several epochs of minibatch gradient steps per
@@ -105,7 +111,19 @@ class _Targets(Node):
         rewards = _device(ctx.eval(model.rewards_placeholder), torch.float32, eng.device).reshape(N, T)
         terminals = _device_bool_u8(ctx.eval(model.terminals_placeholder), eng.device).reshape(N, T)
         st = eng.update_state(N * T)
-        if obj._gae_lambda is None:
+        trunc = ctx.feeds.get(model.truncations_placeholder)
+        if trunc is not None:  # time limits: those terminals keep their bootstrap (module docstring)
+            trunc = _device_bool_u8(trunc, eng.device).reshape(N, T)
+            if obj._gae_lambda is None:
+                gp, bp = obj._tables(T, eng.device)
+                _lib.call('acmi_returns_trunc', _lib.ptr(rewards), _lib.ptr(terminals), _lib.ptr(trunc),
+                          _lib.ptr(fwd.flat_value), _lib.ptr(boot.flat_value), N, T, _lib.ptr(gp), _lib.ptr(bp),
+                          _lib.ptr(st.targets), _lib.ptr(st.adv), eng.stream())
+            else:
+                _lib.call('acmi_gae_trunc', _lib.ptr(rewards), _lib.ptr(terminals), _lib.ptr(trunc),
+                          _lib.ptr(fwd.flat_value), _lib.ptr(boot.flat_value), N, T, obj._gamma, obj._gae_lambda,
+                          _lib.ptr(st.targets), _lib.ptr(st.adv), eng.stream())
+        elif obj._gae_lambda is None:
             gp, bp = obj._tables(T, eng.device)
             _lib.call('acmi_returns', _lib.ptr(rewards), _lib.ptr(terminals), _lib.ptr(fwd.flat_value),
                       _lib.ptr(boot.flat_value), N, T, _lib.ptr(gp), _lib.ptr(bp), _lib.ptr(st.targets),

@@ -15,6 +15,7 @@ constexpr int kCatch = 0, kBreakout = 1;
 constexpr uint32_t CATCH_TAG = 0xCA7C0000u;
 constexpr uint32_t BREAKOUT_TAG = 0xB4EA0000u;
 constexpr int32_t BREAKOUT_MAX_STEPS = 2000;
+constexpr uint8_t kRunning = 0, kGameOver = 1, kLifeLost = 2;  // acmi_game_state_t.done
 
 constexpr int kGameFrameWords = 84 * 84 / 4;  // 16-byte words of a stack: 4 pixels x 4 channels
 constexpr int kGameThreads = 256;
@@ -67,10 +68,13 @@ __device__ __forceinline__ void game_start(int game, uint32_t seed, uint32_t e, 
   game_spawn_ball(game, seed, e, k, v);
 }
 
-// step t (1-based) of the episode under action a; -> reward, terminal
-__device__ __forceinline__ void game_advance(int game, uint32_t seed, uint32_t e, uint32_t k, int32_t t,
-                                             uint32_t action, GameVars& v, float& rew, bool& term) {
+// One step of episode k under action a; -> reward, own (the game ended by its own
+// rules: Catch's ball landed, Breakout ran out of lives or bricks; the step cap is
+// the stepper's business, game_cut) and lost (a life went in this step).
+__device__ __forceinline__ void game_advance(int game, uint32_t seed, uint32_t e, uint32_t k, uint32_t action,
+                                             GameVars& v, float& rew, bool& own, bool& lost) {
   rew = 0.f;
+  lost = false;
   if (game == kCatch) {
     const uint32_t a = action < 3u ? action : 0u;
     if (a == 1u) v.px = min(v.px + 4, 72);
@@ -78,8 +82,8 @@ __device__ __forceinline__ void game_advance(int game, uint32_t seed, uint32_t e
     if (v.bx + v.vx < 0 || v.bx + v.vx > 80) v.vx = -v.vx;
     v.bx += v.vx;
     v.by += 4;
-    term = v.by == 76;
-    if (term) {
+    own = v.by == 76;
+    if (own) {
       const int32_t d = v.bx - v.px;
       rew = (d == 0 || d == 4 || d == 8) ? 1.f : -1.f;
     }
@@ -119,9 +123,28 @@ __device__ __forceinline__ void game_advance(int game, uint32_t seed, uint32_t e
   }
   if (v.by >= 80) {
     v.lives -= 1;
+    lost = true;
     if (v.lives > 0) game_spawn_ball(game, seed, e, k, v);
   }
-  term = v.lives == 0 || (v.b0 | v.b1 | v.b2) == 0u || t >= BREAKOUT_MAX_STEPS;
+  own = v.lives == 0 || (v.b0 | v.b1 | v.b2) == 0u;
+}
+
+// How step t (1-based) of an episode ends under the rules (host.py, "Cuts"): over = the
+// game restarts at the next step, term = what the learner sees, trunc = the cap alone
+// ended it.  max_steps 0: the game's own cap (Breakout 2000, Catch none).
+struct GameCut {
+  bool over, term, trunc;
+};
+__device__ __forceinline__ GameCut game_cut(int game, int32_t episodic_life, int32_t max_steps, int32_t t, bool own,
+                                            bool lost) {
+  const int32_t cap = max_steps > 0 ? max_steps : (game == kBreakout ? BREAKOUT_MAX_STEPS : 0x7fffffff);
+  const bool capped = t >= cap;
+  const bool life = episodic_life != 0 && lost;
+  GameCut c;
+  c.over = own || capped;
+  c.term = c.over || life;
+  c.trunc = capped && !own && !life;
+  return c;
 }
 
 // what a thread needs to draw pixels of a state: sizes and, per pixel, a few compares

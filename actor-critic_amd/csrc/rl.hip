@@ -105,9 +105,12 @@ __global__ void categorical_masked_kernel(const float* logits, int ld, int B, in
 // n-step targets (objectives.py:178-214), one thread per env, reverse-free:
 // target[t] = sum_{i=t..stop} r_i * gp[i-t]  (ascending i, mul+add, no FMA)
 // ---------------------------------------------------------------------------
-__global__ void returns_kernel(const float* r, const uint8_t* d, const float* v,
-                               const float* vb, int N, int T, const float* gp,
-                               const float* bp, float* tgt, float* adv) {
+// TRUNC (acmi_returns_trunc): a terminal flagged in tr still ends the sum but keeps a
+// bootstrap, from the value of the step after it (the lazy auto-reset's observation)
+template <bool TRUNC>
+__device__ __forceinline__ void returns_body(const float* r, const uint8_t* d, const uint8_t* tr, const float* v,
+                                             const float* vb, int N, int T, const float* gp, const float* bp,
+                                             float* tgt, float* adv) {
   // one thread per (env, step): the first terminal at or after t ends the sum
   const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= (long long)N * T) return;
@@ -120,10 +123,26 @@ __global__ void returns_kernel(const float* r, const uint8_t* d, const float* v,
   const int stop = next_term < T ? next_term : T - 1;
   float acc = 0.f;
   for (int i = t; i <= stop; ++i) acc = __fadd_rn(acc, __fmul_rn(rn[i], gp[i - t]));
-  const float boot = next_term < T ? 0.f : __fmul_rn(bp[T - t], vb[n]);
+  float boot = next_term < T ? 0.f : __fmul_rn(bp[T - t], vb[n]);
+  if (TRUNC) {
+    if (next_term < T && tr[(long long)n * T + stop] != 0) {
+      const float vnext = stop + 1 < T ? v[(long long)n * T + stop + 1] : vb[n];
+      boot = __fmul_rn(bp[stop + 1 - t], vnext);
+    }
+  }
   const float target = __fadd_rn(acc, boot);
   tgt[idx] = target;
   adv[idx] = __fsub_rn(target, v[idx]);
+}
+__global__ void returns_kernel(const float* r, const uint8_t* d, const float* v,
+                               const float* vb, int N, int T, const float* gp,
+                               const float* bp, float* tgt, float* adv) {
+  returns_body<false>(r, d, nullptr, v, vb, N, T, gp, bp, tgt, adv);
+}
+__global__ void returns_trunc_kernel(const float* r, const uint8_t* d, const uint8_t* tr, const float* v,
+                                     const float* vb, int N, int T, const float* gp, const float* bp, float* tgt,
+                                     float* adv) {
+  returns_body<true>(r, d, tr, v, vb, N, T, gp, bp, tgt, adv);
 }
 
 // ---------------------------------------------------------------------------
@@ -135,21 +154,35 @@ __global__ void returns_kernel(const float* r, const uint8_t* d, const float* v,
 // restatement (oracle.gae_f32) is bit-exact.  lambda = 1 equals the n-step
 // target in exact arithmetic.
 // ---------------------------------------------------------------------------
-__global__ void gae_kernel(const float* r, const uint8_t* d, const float* v, const float* vb, int N,
-                           int T, float gamma, float gl, float* tgt, float* adv) {
+// TRUNC (acmi_gae_trunc): boot = live || truncated_t keeps gamma V_{t+1} in delta_t at
+// a truncated terminal; the lambda chain is cut at every terminal all the same
+template <bool TRUNC>
+__device__ __forceinline__ void gae_body(const float* r, const uint8_t* d, const uint8_t* tr, const float* v,
+                                         const float* vb, int N, int T, float gamma, float gl, float* tgt,
+                                         float* adv) {
   const int n = blockIdx.x * blockDim.x + threadIdx.x;
   if (n >= N) return;
   float next_v = vb[n], last = 0.f;
   for (int t = T - 1; t >= 0; --t) {
     const long long i = (long long)n * T + t;
     const bool live = d[i] == 0;
+    bool boot = live;
+    if (TRUNC) boot = live || tr[i] != 0;
     const float vi = v[i];
-    const float delta = __fsub_rn(__fadd_rn(r[i], live ? __fmul_rn(gamma, next_v) : 0.f), vi);
+    const float delta = __fsub_rn(__fadd_rn(r[i], boot ? __fmul_rn(gamma, next_v) : 0.f), vi);
     last = __fadd_rn(delta, live ? __fmul_rn(gl, last) : 0.f);
     adv[i] = last;
     tgt[i] = __fadd_rn(last, vi);
     next_v = vi;
   }
+}
+__global__ void gae_kernel(const float* r, const uint8_t* d, const float* v, const float* vb, int N,
+                           int T, float gamma, float gl, float* tgt, float* adv) {
+  gae_body<false>(r, d, nullptr, v, vb, N, T, gamma, gl, tgt, adv);
+}
+__global__ void gae_trunc_kernel(const float* r, const uint8_t* d, const uint8_t* tr, const float* v,
+                                 const float* vb, int N, int T, float gamma, float gl, float* tgt, float* adv) {
+  gae_body<true>(r, d, tr, v, vb, N, T, gamma, gl, tgt, adv);
 }
 
 // ---------------------------------------------------------------------------
@@ -732,6 +765,32 @@ int acmi_gae(const float* rewards, const uint8_t* terminals, const float* values
   hipLaunchKernelGGL(gae_kernel, dim3(cdiv(N, 64)), dim3(64), 0, (hipStream_t)stream, rewards, terminals,
                      values, v_boot, N, T, gamma, gamma * lambda, targets, adv);
   ACMI_LAUNCH_CHECK("acmi_gae");
+  return ACMI_OK;
+}
+
+int acmi_returns_trunc(const float* rewards, const uint8_t* terminals, const uint8_t* truncated,
+                       const float* values, const float* v_boot, int N, int T, const float* gamma_pow,
+                       const float* boot_pow, float* targets, float* adv, acmi_stream_t stream) {
+  ACMI_REQUIRE(rewards && terminals && truncated && values && v_boot && gamma_pow && boot_pow && targets &&
+                   adv && N >= 0 && T >= 1,
+               ACMI_ERR_ARG, "acmi_returns_trunc: bad arguments");
+  if (N == 0) return ACMI_OK;
+  hipLaunchKernelGGL(returns_trunc_kernel, dim3(cdiv((long long)N * T, 256)), dim3(256), 0, (hipStream_t)stream,
+                     rewards, terminals, truncated, values, v_boot, N, T, gamma_pow, boot_pow, targets, adv);
+  ACMI_LAUNCH_CHECK("acmi_returns_trunc");
+  return ACMI_OK;
+}
+
+int acmi_gae_trunc(const float* rewards, const uint8_t* terminals, const uint8_t* truncated, const float* values,
+                   const float* v_boot, int N, int T, float gamma, float lambda, float* targets, float* adv,
+                   acmi_stream_t stream) {
+  ACMI_REQUIRE(rewards && terminals && truncated && values && v_boot && targets && adv && N >= 0 && T >= 1 &&
+                   lambda >= 0.f && lambda <= 1.f,
+               ACMI_ERR_ARG, "acmi_gae_trunc: bad arguments");
+  if (N == 0) return ACMI_OK;
+  hipLaunchKernelGGL(gae_trunc_kernel, dim3(cdiv(N, 64)), dim3(64), 0, (hipStream_t)stream, rewards, terminals,
+                     truncated, values, v_boot, N, T, gamma, gamma * lambda, targets, adv);
+  ACMI_LAUNCH_CHECK("acmi_gae_trunc");
   return ACMI_OK;
 }
 

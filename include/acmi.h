@@ -264,6 +264,29 @@ int acmi_gae(const float* rewards, const uint8_t* terminals, const float* values
              const float* v_boot, int N, int T, float gamma, float lambda,
              float* targets, float* adv, acmi_stream_t stream);
 
+/* Truncation-aware targets (time limits, Pardo et al. 2018): acmi_returns and
+ * acmi_gae plus truncated [N][T] u8, read only where terminals is set.  A
+ * truncated terminal still cuts the return, but keeps its bootstrap from the
+ * value of the next observation, which with lazy auto-reset is already in the
+ * batch: V_{t+1} = values[n][t+1], or v_boot[n] at t = T-1.
+ *   GAE:    live = d_t == 0, boot = live || trunc_t,
+ *           delta_t = (r_t + (boot ? gamma*V_{t+1} : 0)) - V_t,
+ *           A_t = delta_t + (live ? gamma*lambda*A_{t+1} : 0), target = A_t + V_t;
+ *   n-step: stop as acmi_returns; the bootstrap term is
+ *           boot_pow[stop+1-t]*V_{stop+1} when stop is a truncated terminal,
+ *           boot_pow[T-t]*v_boot when there is no terminal, else 0.
+ * float32, no contraction, in that order; truncated all zero: the bytes of
+ * acmi_returns / acmi_gae (one kernel body each). */
+int acmi_returns_trunc(const float* rewards, const uint8_t* terminals,
+                       const uint8_t* truncated, const float* values,
+                       const float* v_boot, int N, int T, const float* gamma_pow,
+                       const float* boot_pow, float* targets, float* adv,
+                       acmi_stream_t stream);
+int acmi_gae_trunc(const float* rewards, const uint8_t* terminals,
+                   const uint8_t* truncated, const float* values, const float* v_boot,
+                   int N, int T, float gamma, float lambda, float* targets,
+                   float* adv, acmi_stream_t stream);
+
 /* Advantage normalisation (an option beyond the reference, which has none,
  * objectives.py:128-130): moments[0..1] = (sum, sum of squares) of adv[0..M)
  * in double, fixed order (ws: acmi_adv_moments_ws_doubles(M) doubles).  A
@@ -591,6 +614,38 @@ int acmi_game_step(const acmi_game_state_t* st, int N, int env_offset,
                    int64_t in_stride, uint8_t* obs_out, int64_t out_stride,
                    float* rewards, uint8_t* terminals, float* episode_rewards,
                    int64_t ld, acmi_stream_t stream);
+
+/* acmi_game_step under rules that separate "cut the return here" from "the
+ * game restarts" (host.py, "Cuts"; the reference's AtariEpisodicLifeWrapper,
+ * envs/atari/wrappers.py:89-117, and a time limit that is not a terminal).
+ *   game over  = the game's own end (Catch: the ball landed; Breakout: no
+ *                lives or no bricks) or step >= cap, cap = max_steps, or the
+ *                game's own with 0 (Breakout 2000, Catch none);
+ *   terminals  = game over, or (episodic_life and a life went in this step):
+ *                the learner's terminal, which also zero-fills the old
+ *                channels of the stack;
+ *   truncated  = step >= cap and not the game's own end and not a life cut:
+ *                the cap alone ended the episode (nullable: not written);
+ *   episode_rewards = the whole game's total at a game-over step (a truncated
+ *                one included), the quiet NaN otherwise (life cuts included).
+ * done becomes a code: 0 running, 1 game over (the next step resets lazily, as
+ * acmi_game_step), 2 life lost (the next step restarts the stack from the
+ * current state's frame repeated 4x -- FrameStackWrapper.reset -- and the game,
+ * episode, step and total go on).  Only this entry point writes 2.  Rules
+ * {0, 0} with truncated == NULL write the bytes of acmi_game_step (one kernel).
+ * rules == NULL, episodic_life outside {0, 1} or max_steps outside 0..2000:
+ * ACMI_ERR_ARG, nothing enqueued. */
+typedef struct acmi_game_rules {
+  int32_t episodic_life; /* 1: a lost life is a terminal for the learner    */
+  int32_t max_steps;     /* step cap 1..2000; 0 = the game's own             */
+} acmi_game_rules_t;
+
+int acmi_game_step_cuts(const acmi_game_state_t* st, const acmi_game_rules_t* rules,
+                        int N, int env_offset, uint32_t seed, const int32_t* actions,
+                        const uint8_t* obs_in, int64_t in_stride, uint8_t* obs_out,
+                        int64_t out_stride, float* rewards, uint8_t* terminals,
+                        uint8_t* truncated, float* episode_rewards, int64_t ld,
+                        acmi_stream_t stream);
 
 /* ------------------------------------------------------------------------
  * Atari frame preprocessing for real (raw RGB) frames, batched over envs:

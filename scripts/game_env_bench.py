@@ -5,6 +5,8 @@
          the same 28 KB in + 28 KB out per env.  HIP events over --calls back-to-back
          launches, the cases in alternating rounds; us per launch and the GB/s of the
          stack traffic (2 * 28224 * N bytes a launch, computed from the shape).
+         catch-cuts / breakout-cuts: acmi_game_step_cuts with every option on (episodic
+         life, a step cap, the truncated array written).
   iter   the unfused 32 x 5 A2C iteration (rollout + update, a host clock around a device
          synchronise) on catch against the synthetic stepper forced onto the same
          unfused path (ACMI_ROLLOUT_FUSED=0), and the synthetic stepper's default
@@ -36,6 +38,12 @@ def cmd_step(args):
     dev = torch.device('cuda:0')
     envs = {'synthetic': SyntheticAtariEnvs(N, num_actions=4, seed=1), 'catch': DeviceGameEnvs('catch', N, seed=1),
             'breakout': DeviceGameEnvs('breakout', N, seed=1)}
+    if not args.no_cuts:
+        for g in ('catch', 'breakout'):
+            envs[g + '-cuts'] = DeviceGameEnvs(g, N, seed=1, episodic_life=True, max_episode_steps=1000)
+    if args.cases:
+        envs = {k: envs[k] for k in args.cases}
+    trunc = torch.zeros(N, dtype=torch.uint8, device=dev)
     actions = torch.randint(0, 3, (N,), dtype=torch.int32, device=dev)
     rew = torch.zeros(N, device=dev)
     term = torch.zeros(N, dtype=torch.uint8, device=dev)
@@ -46,7 +54,8 @@ def cmd_step(args):
 
     def launch(k):
         p = obs[k].data_ptr()
-        envs[k].step_into(actions.data_ptr(), p, OBS, p, OBS, rew.data_ptr(), term.data_ptr(), ep.data_ptr(), 1)
+        kw = {'trunc_ptr': trunc.data_ptr()} if k.endswith('-cuts') else {}
+        envs[k].step_into(actions.data_ptr(), p, OBS, p, OBS, rew.data_ptr(), term.data_ptr(), ep.data_ptr(), 1, **kw)
 
     for k in envs:  # warm-up
         for _ in range(50):
@@ -121,6 +130,11 @@ def main():
     st.add_argument('--envs', type=int, default=1024)
     st.add_argument('--calls', type=int, default=500)
     st.add_argument('--rounds', type=int, default=3)
+    st.add_argument('--cases', nargs='+', default=None,
+                    help='only these cases (synthetic, catch, breakout, catch-cuts, breakout-cuts): a kernel '
+                         'trace of one case per process tells the kernels of the two entry points apart')
+    st.add_argument('--no-cuts', action='store_true',
+                    help='leave the -cuts cases out (an older libacmi under ACMI_LIB has no acmi_game_step_cuts)')
     st.set_defaults(fn=cmd_step)
     it = sub.add_parser('iter')
     it.add_argument('--env', choices=('catch', 'synthetic-unfused', 'synthetic'), default='catch')

@@ -7,6 +7,10 @@ every --every updates, plays a separate batch of envs with the greedy policy
 return, after a first line with the uniform policy's.  The lines also go to --out.
 
     python scripts/learn_games.py --algo a2c --game catch --updates 2000 --every 250 --seeds 1 2 3
+
+--episodic-life and --max-episode-steps N train under those rules (DeviceGameEnvs); the
+evaluation envs never take episodic life (evaluate counts terminals as finished games), so
+returns stay whole-game returns and compare across the settings.
 """
 import argparse
 import json
@@ -28,13 +32,16 @@ def run(args, seed, emit):
     torch.cuda.set_device(0)
     sess.reset_default_graph()
     N, T, E = args.envs, args.steps, args.episodes
-    head = dict(algo=args.algo, game=args.game, seed=seed, envs=N, steps=T, eval_envs=args.eval_envs, eval_episodes=E)
+    head = dict(algo=args.algo, game=args.game, seed=seed, envs=N, steps=T, eval_envs=args.eval_envs, eval_episodes=E,
+                episodic_life=args.episodic_life, max_episode_steps=args.max_episode_steps)
+    rules = dict(episodic_life=args.episodic_life, max_episode_steps=args.max_episode_steps)
 
     def stats(returns):
         r = returns.double().flatten()
         return dict(mean_return=round(float(r.mean()), 4), var=round(float(r.var(unbiased=True)), 4), n=r.numel())
 
-    eval_envs = lambda: DeviceGameEnvs(args.game, args.eval_envs, seed=1000 + seed)
+    eval_envs = lambda: DeviceGameEnvs(args.game, args.eval_envs, seed=1000 + seed,
+                                       max_episode_steps=args.max_episode_steps)
     emit(dict(head, policy='uniform', updates=0, env_steps=0, **stats(evaluate(None, eval_envs(), E, uniform=True,
                                                                                  seed=seed))))
     t0 = time.perf_counter()
@@ -49,10 +56,10 @@ def run(args, seed, emit):
 
     if args.algo == 'ppo':
         train_ppo(args.game, N, T, None, args.game, max_updates=args.updates, seed=seed, game=args.game,
-                  on_update=on_update)
+                  on_update=on_update, **rules)
     else:
         train_a2c_acktr(args.algo == 'acktr', args.game, N, T, None, args.game, max_updates=args.updates, seed=seed,
-                        game=args.game, on_update=on_update)
+                        game=args.game, on_update=on_update, **rules)
 
 
 def main():
@@ -67,6 +74,8 @@ def main():
     ap.add_argument('--eval-envs', type=int, default=32)
     ap.add_argument('--episodes', type=int, default=8, help='evaluation episodes per env')
     ap.add_argument('--sample', action='store_true', help='evaluate draws from the policy instead of its mode')
+    ap.add_argument('--episodic-life', action='store_true', help='train with a lost life as a terminal')
+    ap.add_argument('--max-episode-steps', type=int, default=None, help='step cap (truncation), 1..2000')
     ap.add_argument('--out', default=None, help='also append the JSON lines to this file')
     args = ap.parse_args()
     if args.steps is None:
