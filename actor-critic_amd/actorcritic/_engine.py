@@ -12,7 +12,7 @@ import weakref
 import numpy as np
 import torch
 
-from actorcritic import _lib
+from actorcritic import _lib, _ops
 
 OBS_SHAPE = (84, 84, 4)
 OBS_BYTES = 84 * 84 * 4
@@ -329,15 +329,10 @@ class NetEngine(object):
         """side: run on UpdateState.side()'s stream and workspace (see there)."""
         net = self.net()
         bwd, ws = (side.bwd, side.ws) if side is not None else (st.bwd, st.bwd_ws)
-        if self.masks is not None:  # y ~ Cat over each row's legal set
-            _lib.call('acmi_kfac_output_stats_masked', ctypes.byref(net), fwd.M, ctypes.byref(fwd.acts.struct),
-                      ctypes.byref(bwd), seed, self.rank * fwd.M, counter,
-                      _lib.ptr(self.row_masks(fwd.batch, fwd.steps)), _lib.ptr(st.gstat), _lib.ptr(ws), ws.numel(),
-                      self.stream())
-            return
-        _lib.call('acmi_kfac_output_stats', ctypes.byref(net), fwd.M, ctypes.byref(fwd.acts.struct),
-                  ctypes.byref(bwd), seed, self.rank * fwd.M, counter, _lib.ptr(st.gstat), _lib.ptr(ws),
-                  ws.numel(), self.stream())
+        # with masks: y ~ Cat over each row's legal set
+        legal = None if self.masks is None else self.row_masks(fwd.batch, fwd.steps)
+        _ops.output_stats(net, fwd.M, fwd.acts.struct, bwd, seed, self.rank * fwd.M, counter, st.gstat, ws,
+                          ws.numel(), self.stream(), legal=legal)
 
     # the G chain on a side stream: '1' always, '0' never, unset: at batches up to
     # CONCURRENT_STATS_ROWS.  Round 6 at the bench shard (512 x 20, same lease):
@@ -525,16 +520,10 @@ class NetEngine(object):
         return acts, obs
 
     def sample(self, logits, B, out, mode=False, seed=0, stream_id=0, uniforms=None, ld=None):
-        if self.masks is not None:
-            _lib.call('acmi_sample_actions_masked', ctypes.c_void_p(logits.data_ptr()), ld or self.A, B, self.A,
-                      seed, stream_id, None, self.sample_counter, 0, _lib.ptr(uniforms), 1 if mode else 0,
-                      _lib.ptr(self.row_masks(B)), ctypes.c_void_p(out.data_ptr()),
-                      ctypes.c_void_p(self._bad_rows.data_ptr()), self.stream())
-            self.sample_counter += 1
-            return
-        _lib.call('acmi_sample_actions', ctypes.c_void_p(logits.data_ptr()), ld or self.A, B, self.A, seed,
-                  stream_id, self.sample_counter, _lib.ptr(uniforms), 1 if mode else 0,
-                  ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(self._bad_rows.data_ptr()), self.stream())
+        legal = None if self.masks is None else self.row_masks(B)
+        _ops.sample_actions(logits.data_ptr(), ld or self.A, B, self.A, seed, stream_id, self.sample_counter, 0,
+                            out.data_ptr(), self._bad_rows.data_ptr(), self.stream(), legal=legal,
+                            uniforms=uniforms, mode=mode)
         self.sample_counter += 1
 
     def check_bad_rows(self):

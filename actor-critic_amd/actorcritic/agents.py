@@ -13,9 +13,9 @@ else takes the reference's list-based loop.
 Two opt-in variants, bit-identical to the one-chain rollout (test_two_stream_rollout_
 is_bit_identical, and across updates test_rollout_variants_give_identical_updates):
 ACMI_ROLLOUT_SPLIT=1 runs the two env halves as two chains on two HIP streams (the
-sampler keys its RNG by the global row, acmi_sample_actions_at, the stepper by the global
+sampler keys its RNG by the global row, its row_offset, the stepper by the global
 env id); ACMI_ROLLOUT_GRAPH=1 captures the rollout once as a hipGraph and replays it (the
-RNG counter read from device memory, acmi_sample_actions_dev).  Neither is faster on one
+RNG counter read from device memory, the sampler's counter_dev).  Neither is faster on one
 MI355X (same lease, two rounds each: 512 x 20 2.68 vs 2.69-2.70 M env-steps/s split on /
 off; 1024 x 20 bf16 2.72-2.75 M both): the per-step kernels are GPU-bound and the host
 keeps up.  They are kept for hosts where launch overhead is not hidden.  (An earlier
@@ -31,7 +31,7 @@ from abc import ABCMeta, abstractmethod
 
 import torch
 
-from actorcritic import _lib
+from actorcritic import _lib, _ops
 from actorcritic._engine import OBS_BYTES
 
 
@@ -257,39 +257,11 @@ class MultiEnvAgent(Agent):
                 eng.check_bad_rows()
         if self._observations is None:
             env.reset_into(rb.next_obs.data_ptr())
-        stream = eng.stream()
-        A = eng.A
-        legal = _mask_rows(eng, N)
-        obs0 = rb.obs.data_ptr()
-        rew0, term0, ep0 = rb.rewards.data_ptr(), rb.terminals.data_ptr(), rb.episode_rewards.data_ptr()
         seed = (self._model._random_seed or 0) & 0xFFFFFFFF
         if rb.use_graph:
-            self._rollout_graph(eng, env, rb, N, T, A, seed)
-        elif rb.halves or rb.fused:
-            self._rollout_halves(eng, env, rb, N, T, A, seed)
+            self._rollout_graph(eng, env, rb, N, T, eng.A, seed)
         else:
-            rb.obs[:, 0].copy_(rb.next_obs)
-            for t in range(T):
-                src = obs0 + t * OBS_BYTES
-                eng.forward(src, N, rb.acts.view(t, T), want_value=True, img_stride=T * OBS_BYTES, act_stride=T)
-                act_t = rb.actions_tn[t]
-                if legal is not None:
-                    _lib.call('acmi_sample_actions_masked', _lib.c_vp(rb.acts.logits.data_ptr() + 4 * t * A), T * A,
-                              N, A, seed, 0, None, eng.sample_counter & 0xFFFFFFFF, eng.rank * N, None, 0,
-                              _lib.c_vp(legal), _lib.c_vp(act_t.data_ptr()), _lib.c_vp(eng._bad_rows.data_ptr()),
-                              stream)
-                else:
-                    _lib.call('acmi_sample_actions_at', _lib.c_vp(rb.acts.logits.data_ptr() + 4 * t * A), T * A, N,
-                              A, seed, 0, eng.sample_counter, eng.rank * N, None, 0, _lib.c_vp(act_t.data_ptr()),
-                              _lib.c_vp(eng._bad_rows.data_ptr()), stream)
-                eng.sample_counter += 1
-                if t + 1 < T:
-                    dst, dstride = obs0 + (t + 1) * OBS_BYTES, T * OBS_BYTES
-                else:
-                    dst, dstride = rb.next_obs.data_ptr(), OBS_BYTES
-                env.step_into(act_t.data_ptr(), src, T * OBS_BYTES, dst, dstride, rew0 + 4 * t, term0 + t,
-                              ep0 + 4 * t, T, **_trunc_arg(rb, t))
-            rb.actions.copy_(rb.actions_tn.t())
+            self._rollout_halves(eng, env, rb, N, T, eng.A, seed)
         rb.bad_host.copy_(eng._bad_counts, non_blocking=True)
         rb.bad_event = torch.cuda.Event()
         rb.bad_event.record()
@@ -320,14 +292,8 @@ class MultiEnvAgent(Agent):
             src = obs0 + t * OBS_BYTES
             eng.forward(src, N, rb.acts.view(t, T), want_value=True, img_stride=T * OBS_BYTES, act_stride=T)
             row = hb.act_bad[t]  # [actions of step t (N) | rows with non-finite logits (1)]
-            if legal is not None:
-                _lib.call('acmi_sample_actions_masked', _lib.c_vp(rb.acts.logits.data_ptr() + 4 * t * A), T * A, N,
-                          A, seed, 0, None, eng.sample_counter & 0xFFFFFFFF, eng.rank * N, None, 0,
-                          _lib.c_vp(legal), _lib.c_vp(row.data_ptr()), _lib.c_vp(row.data_ptr() + 4 * N), stream)
-            else:
-                _lib.call('acmi_sample_actions_at', _lib.c_vp(rb.acts.logits.data_ptr() + 4 * t * A), T * A, N, A,
-                          seed, 0, eng.sample_counter & 0xFFFFFFFF, eng.rank * N, None, 0,
-                          _lib.c_vp(row.data_ptr()), _lib.c_vp(row.data_ptr() + 4 * N), stream)
+            _ops.sample_actions(rb.acts.logits.data_ptr() + 4 * t * A, T * A, N, A, seed, 0, eng.sample_counter,
+                                eng.rank * N, row.data_ptr(), row.data_ptr() + 4 * N, stream, legal=legal)
             eng.sample_counter += 1
             hb.act_bad_host.copy_(row, non_blocking=True)
             hb.event.record()
@@ -422,25 +388,12 @@ def _half_step(eng, env, rb, h, N2, T, A, t, seed, dev_ctr=False, fuse=False):
                             env.env_offset + n0, env.seed, dst, dstride, rew, term, ep, T,
                             1 if fuse and t > 0 else 0, ctypes.addressof(nxt) if nxt is not None else None, T,
                             src if t == 0 else None)
-        if legal is not None:
-            _lib.call('acmi_rollout_step_masked', ctypes.byref(eng.net()), ctypes.c_void_p(src_t), sstride, N2,
-                      ctypes.byref(acts), T, ctypes.byref(io), _lib.c_vp(legal), eng.stream())
-        else:
-            _lib.call('acmi_rollout_step', ctypes.byref(eng.net()), ctypes.c_void_p(src_t), sstride, N2,
-                      ctypes.byref(acts), T, ctypes.byref(io), eng.stream())
+        _ops.rollout_step(eng.net(), src_t, sstride, N2, acts, T, io, eng.stream(), legal=legal)
         return
     eng.forward(src, N2, acts, want_value=True, img_stride=T * OBS_BYTES, act_stride=T)
-    trunc = _trunc_arg(rb, row)
-    if legal is not None:
-        _lib.call('acmi_sample_actions_masked', _lib.c_vp(rb.acts.logits.data_ptr() + 4 * row * A), T * A, N2, A,
-                  seed, 0, ctr_dev, ctr, row0, None, 0, _lib.c_vp(legal), _lib.c_vp(act_t),
-                  _lib.c_vp(eng._bad_rows.data_ptr()), eng.stream())
-        env.step_range_into(n0, N2, act_t, src, T * OBS_BYTES, dst, dstride, rew, term, ep, T, **trunc)
-        return
-    _lib.call('acmi_sample_actions_dev', _lib.c_vp(rb.acts.logits.data_ptr() + 4 * row * A), T * A, N2, A,
-              seed, 0, ctr_dev, ctr, row0, None, 0, _lib.c_vp(act_t),
-              _lib.c_vp(eng._bad_rows.data_ptr()), eng.stream())
-    env.step_range_into(n0, N2, act_t, src, T * OBS_BYTES, dst, dstride, rew, term, ep, T, **trunc)
+    _ops.sample_actions(rb.acts.logits.data_ptr() + 4 * row * A, T * A, N2, A, seed, 0, ctr, row0, act_t,
+                        eng._bad_rows.data_ptr(), eng.stream(), legal=legal, counter_dev=ctr_dev)
+    env.step_range_into(n0, N2, act_t, src, T * OBS_BYTES, dst, dstride, rew, term, ep, T, **_trunc_arg(rb, row))
 
 
 def transpose_list(values):

@@ -10,7 +10,7 @@ import torch
 
 from actorcritic import spaces
 from actorcritic._engine import NetEngine, _as_obs, check_mask_count
-from actorcritic import _lib
+from actorcritic import _ops
 from actorcritic.baselines import StateValueFunction
 from actorcritic.model import ActorCriticModel
 from actorcritic.policies import SoftmaxPolicy
@@ -50,13 +50,8 @@ class ForwardOut(object):
 
     def entropy(self):
         out = torch.empty(self.M, dtype=torch.float32, device=self.engine.device)
-        legal = self.row_masks()
-        if legal is not None:
-            _lib.call('acmi_categorical_masked', _lib.ptr(self.flat_logits), self.engine.A, self.M, self.engine.A,
-                      None, _lib.ptr(legal), _lib.ptr(out), None, self.engine.stream())
-            return out.reshape(self.batch, self.steps)
-        _lib.call('acmi_categorical', _lib.ptr(self.flat_logits), self.engine.A, self.M, self.engine.A, None,
-                  _lib.ptr(out), None, self.engine.stream())
+        _ops.categorical(self.flat_logits, self.engine.A, self.M, self.engine.A, None, out, None,
+                         self.engine.stream(), legal=self.row_masks())
         return out.reshape(self.batch, self.steps)
 
     def log_prob(self, actions):
@@ -64,13 +59,8 @@ class ForwardOut(object):
         if a.numel() != self.M:
             raise ValueError('actions shape does not match the observations')
         out = torch.empty(self.M, dtype=torch.float32, device=self.engine.device)
-        legal = self.row_masks()
-        if legal is not None:
-            _lib.call('acmi_categorical_masked', _lib.ptr(self.flat_logits), self.engine.A, self.M, self.engine.A,
-                      _lib.ptr(a), _lib.ptr(legal), None, _lib.ptr(out), self.engine.stream())
-            return out.reshape(self.batch, self.steps)
-        _lib.call('acmi_categorical', _lib.ptr(self.flat_logits), self.engine.A, self.M, self.engine.A, _lib.ptr(a),
-                  None, _lib.ptr(out), self.engine.stream())
+        _ops.categorical(self.flat_logits, self.engine.A, self.M, self.engine.A, a, None, out,
+                         self.engine.stream(), legal=self.row_masks())
         return out.reshape(self.batch, self.steps)
 
 

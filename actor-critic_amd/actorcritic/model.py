@@ -55,7 +55,7 @@ class ActorCriticModel(object, metaclass=ABCMeta):
     def truncations_placeholder(self):
         """Optional, beyond the reference's five: bool [env, step], set where a terminal is
         a time-limit truncation.  Fed, the objectives' targets keep the bootstrap from the
-        next observation's value at those steps (acmi_returns_trunc / acmi_gae_trunc);
+        next observation's value at those steps (the truncating acmi_returns / acmi_gae);
         unfed, every terminal cuts it, as in the reference."""
         return self._truncations_placeholder
 

@@ -20,7 +20,8 @@ Time limits (beyond the reference as well): when ``model.truncations_placeholder
 fed (bool [env, step]: the terminals that a step cap alone caused, ``MultiEnvAgent.
 last_truncations``), those terminals still cut the return but keep the bootstrap from
 the value of the next observation -- row t+1 of the batch, or the bootstrap row at
-t = T-1 -- through acmi_returns_trunc / acmi_gae_trunc.  Unfed, every terminal cuts it.
+t = T-1 -- through the truncating forms of acmi_returns / acmi_gae (_ops.targets).
+Unfed, every terminal cuts it.
 
 :class:`PPOObjective` (also beyond the reference) shares those targets and
 advantages and replaces the loss by PPO's clipped surrogate (acmi_ppo_loss); its
@@ -34,7 +35,7 @@ from abc import ABCMeta, abstractmethod
 import numpy as np
 import torch
 
-from actorcritic import _lib
+from actorcritic import _lib, _ops
 from actorcritic.session import Node, as_node
 
 
@@ -114,24 +115,9 @@ class _Targets(Node):
         trunc = ctx.feeds.get(model.truncations_placeholder)
         if trunc is not None:  # time limits: those terminals keep their bootstrap (module docstring)
             trunc = _device_bool_u8(trunc, eng.device).reshape(N, T)
-            if obj._gae_lambda is None:
-                gp, bp = obj._tables(T, eng.device)
-                _lib.call('acmi_returns_trunc', _lib.ptr(rewards), _lib.ptr(terminals), _lib.ptr(trunc),
-                          _lib.ptr(fwd.flat_value), _lib.ptr(boot.flat_value), N, T, _lib.ptr(gp), _lib.ptr(bp),
-                          _lib.ptr(st.targets), _lib.ptr(st.adv), eng.stream())
-            else:
-                _lib.call('acmi_gae_trunc', _lib.ptr(rewards), _lib.ptr(terminals), _lib.ptr(trunc),
-                          _lib.ptr(fwd.flat_value), _lib.ptr(boot.flat_value), N, T, obj._gamma, obj._gae_lambda,
-                          _lib.ptr(st.targets), _lib.ptr(st.adv), eng.stream())
-        elif obj._gae_lambda is None:
-            gp, bp = obj._tables(T, eng.device)
-            _lib.call('acmi_returns', _lib.ptr(rewards), _lib.ptr(terminals), _lib.ptr(fwd.flat_value),
-                      _lib.ptr(boot.flat_value), N, T, _lib.ptr(gp), _lib.ptr(bp), _lib.ptr(st.targets),
-                      _lib.ptr(st.adv), eng.stream())
-        else:
-            _lib.call('acmi_gae', _lib.ptr(rewards), _lib.ptr(terminals), _lib.ptr(fwd.flat_value),
-                      _lib.ptr(boot.flat_value), N, T, obj._gamma, obj._gae_lambda, _lib.ptr(st.targets),
-                      _lib.ptr(st.adv), eng.stream())
+        tables = obj._tables(T, eng.device) if obj._gae_lambda is None else None
+        _ops.targets(rewards, terminals, fwd.flat_value, boot.flat_value, N, T, obj._gamma, obj._gae_lambda, tables,
+                     st.targets, st.adv, eng.stream(), truncated=trunc)
         if obj._normalize:
             _normalize_advantages(eng, st.adv, N * T, obj._adv_eps)
         st.fwd = fwd
@@ -177,18 +163,10 @@ class _Loss(Node):
         # global means once the update's all-reduce has summed them (loss_reduced)
         st.loss_reduced = eng.world_size == 1
         st.fwd = fwd
-        legal = fwd.row_masks()
-        if legal is not None:  # over each row's legal set; bad rows count in the engine's counter
-            _lib.call('acmi_a2c_loss_masked', _lib.ptr(fwd.flat_logits), eng.A, _lib.ptr(fwd.flat_value),
-                      _lib.ptr(actions), _lib.ptr(st.targets), _lib.ptr(st.adv), M, eng.A, float(obj._beta),
-                      float(obj._vcoef), 1.0 / eng.world_size, _lib.ptr(st.dhead), eng.ldh, _lib.ptr(st.loss_ws),
-                      _lib.ptr(st.loss), _lib.ptr(legal), _lib.ptr(eng._mask_bad_rows), eng.stream())
-            return st.loss
-        _lib.call('acmi_a2c_loss', _lib.ptr(fwd.flat_logits), eng.A, _lib.ptr(fwd.flat_value), _lib.ptr(actions),
-                  _lib.ptr(st.targets), _lib.ptr(st.adv), M, eng.A, float(obj._beta), float(obj._vcoef),
-                  1.0 / eng.world_size, _lib.ptr(st.dhead), eng.ldh, _lib.ptr(st.loss_ws), _lib.ptr(st.loss),
-                  eng.stream())
-        st.fwd = fwd
+        # with masks: over each row's legal set; bad rows count in the engine's counter
+        _ops.a2c_loss(fwd.flat_logits, eng.A, fwd.flat_value, actions, st.targets, st.adv, M, eng.A,
+                      float(obj._beta), float(obj._vcoef), 1.0 / eng.world_size, st.dhead, eng.ldh, st.loss_ws,
+                      st.loss, eng.stream(), legal=fwd.row_masks(), bad_rows=eng._mask_bad_rows)
         return st.loss
 
     def scalars(self, ctx):
@@ -375,12 +353,7 @@ class _PPOBatch(Node):
         if bufs is None:
             bufs = obj._buffers[M] = _PPOBuffers(eng, M)
         masks = fwd.row_masks()
-        if masks is not None:
-            _lib.call('acmi_categorical_masked', _lib.ptr(fwd.flat_logits), eng.A, M, eng.A, _lib.ptr(actions),
-                      _lib.ptr(masks), None, _lib.ptr(bufs.old_logp), eng.stream())
-        else:
-            _lib.call('acmi_categorical', _lib.ptr(fwd.flat_logits), eng.A, M, eng.A, _lib.ptr(actions), None,
-                      _lib.ptr(bufs.old_logp), eng.stream())
+        _ops.categorical(fwd.flat_logits, eng.A, M, eng.A, actions, None, bufs.old_logp, eng.stream(), legal=masks)
         bufs.old_values.copy_(fwd.flat_value)
         return _PPORun(st, fwd, actions, bufs, masks)
 
@@ -476,23 +449,15 @@ class PPOObjective(ActorCriticObjective):
         """acmi_ppo_loss of ``fwd``, a forward of the rows row0 .. row0+rows-1 of the batch
         whose (actions, old_logp, old_values, targets, adv) ``vectors`` are: the run's
         own (:meth:`_PPORun.vectors`) or their shuffled copy (:class:`_PPORowBuffers`);
-        a sixth vector holds the rows' legal-action words: acmi_ppo_loss_masked."""
+        a sixth vector holds the rows' legal-action words: the loss over each row's legal set."""
         eng = self._model.engine
         sl = slice(row0, row0 + rows)
         actions, old_logp, old_values, targets, adv = (v[sl] for v in vectors[:5])
-        if len(vectors) > 5:
-            _lib.call('acmi_ppo_loss_masked', _lib.ptr(fwd.flat_logits), eng.A, _lib.ptr(fwd.flat_value),
-                      _lib.ptr(actions), _lib.ptr(old_logp), _lib.ptr(old_values),
-                      _lib.ptr(targets), _lib.ptr(adv), rows, eng.A, self._clip, self._vclip,
-                      self._beta, float(self._vcoef), 1.0 / eng.world_size, _lib.ptr(dhead), eng.ldh,
-                      _lib.ptr(bufs.loss_ws(eng, rows)), _lib.ptr(loss_out), _lib.ptr(clip_frac_out),
-                      _lib.ptr(vectors[5][sl]), _lib.ptr(eng._mask_bad_rows), eng.stream())
-            return
-        _lib.call('acmi_ppo_loss', _lib.ptr(fwd.flat_logits), eng.A, _lib.ptr(fwd.flat_value),
-                  _lib.ptr(actions), _lib.ptr(old_logp), _lib.ptr(old_values),
-                  _lib.ptr(targets), _lib.ptr(adv), rows, eng.A, self._clip, self._vclip,
-                  self._beta, float(self._vcoef), 1.0 / eng.world_size, _lib.ptr(dhead), eng.ldh,
-                  _lib.ptr(bufs.loss_ws(eng, rows)), _lib.ptr(loss_out), _lib.ptr(clip_frac_out), eng.stream())
+        legal = vectors[5][sl] if len(vectors) > 5 else None
+        _ops.ppo_loss(fwd.flat_logits, eng.A, fwd.flat_value, actions, old_logp, old_values, targets, adv, rows,
+                      eng.A, self._clip, self._vclip, self._beta, float(self._vcoef), 1.0 / eng.world_size, dhead,
+                      eng.ldh, bufs.loss_ws(eng, rows), loss_out, clip_frac_out, eng.stream(), legal=legal,
+                      bad_rows=eng._mask_bad_rows)
 
     def optimize_shared(self, optimizer, baseline_loss_weight=0.5, num_epochs=4, num_minibatches=4, shuffle_seed=0,
                         step_callback=None, global_step=None, minibatch='envs', **kwargs):

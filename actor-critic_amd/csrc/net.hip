@@ -520,30 +520,21 @@ static int backward_impl(const Layout& L, const float* P, const uint8_t* obs,
 // MASKED (acmi_kfac_output_stats_masked): y ~ Cat over the row's legal set S with
 // the same key, p - onehot(y) on S and +0 elsewhere (stepper.hpp legal_at)
 template <bool MASKED>
-__device__ __forceinline__ void sampled_head_grad_body(const float* logits, int ld, int B, int A,
-                                                       uint32_t seed, uint32_t row0, uint32_t ctr,
-                                                       float* g, int ldg, const uint32_t* legal) {
+__global__ void sampled_head_grad_kernel(const float* logits, int ld, int B, int A, uint32_t seed, uint32_t row0,
+                                         uint32_t ctr, float* g, int ldg, const uint32_t* legal) {
   const int m = blockIdx.x * blockDim.x + threadIdx.x;
   if (m >= B) return;
   const float* z = logits + (long long)m * ld;
   const uint32_t lg = MASKED ? legal_bits(legal[m], A) : 0xFFFFFFFFu;
-  float mx = -INFINITY;
-  int last = MASKED ? -1 : A - 1;
-  for (int a = 0; a < A; ++a) {
-    if (!legal_at<MASKED>(lg, a)) continue;
-    if (MASKED) last = a;
-    mx = fmaxf(mx, z[a]);
-  }
-  float se = 0.f;
-  for (int a = 0; a < A; ++a)
-    if (legal_at<MASKED>(lg, a)) se += expf(z[a] - mx);
+  const RowMaxSum ms = row_max_sum<MASKED>(z, A, lg);
+  const float mx = ms.mx, se = ms.se;
   // keyed by the global row: a data-parallel shard draws what the full batch would
   const uint32_t h = key4(seed, 0u, ctr, row0 + (uint32_t)m);
   const float u = u01(h);
   // inverse CDF draw
   const float target = u * se;
   float c = 0.f;
-  int y = last;
+  int y = ms.last;
   for (int a = 0; a < A; ++a) {
     if (!legal_at<MASKED>(lg, a)) continue;
     c += expf(z[a] - mx);
@@ -559,15 +550,11 @@ __device__ __forceinline__ void sampled_head_grad_body(const float* logits, int 
   gr[A] = -eps;
   for (int a = A + 1; a < ldg; ++a) gr[a] = 0.f;
 }
-__global__ void sampled_head_grad_kernel(const float* logits, int ld, int B, int A,
-                                         uint32_t seed, uint32_t row0, uint32_t ctr,
-                                         float* g, int ldg) {
-  sampled_head_grad_body<false>(logits, ld, B, A, seed, row0, ctr, g, ldg, nullptr);
-}
-__global__ void sampled_head_grad_masked_kernel(const float* logits, int ld, int B, int A,
-                                                uint32_t seed, uint32_t row0, uint32_t ctr,
-                                                float* g, int ldg, const uint32_t* legal) {
-  sampled_head_grad_body<true>(logits, ld, B, A, seed, row0, ctr, g, ldg, legal);
+// legal (nullable): per-row legal-action words
+static void launch_sampled_head_grad(const float* logits, int ld, int B, int A, uint32_t seed, uint32_t row0,
+                                     uint32_t ctr, float* g, int ldg, const uint32_t* legal, hipStream_t s) {
+  const auto kern = legal ? sampled_head_grad_kernel<true> : sampled_head_grad_kernel<false>;
+  hipLaunchKernelGGL(kern, dim3(cdiv(B, 128)), dim3(128), 0, s, logits, ld, B, A, seed, row0, ctr, g, ldg, legal);
 }
 
 template <int C3>
@@ -591,12 +578,7 @@ static int output_stats_impl(const Layout& L, const float* P, int B,
   const bool g1_fits = (long long)convt2_gram_blocks(B) * 33 * 32 <= cap;
   int rc = ACMI_OK;
   if (stage == 0) {
-    if (legal)
-      hipLaunchKernelGGL(sampled_head_grad_masked_kernel, dim3(cdiv(B, 128)), dim3(128), 0, s,
-                         a->logits, a->ld_logits, B, L.A, seed, row0, ctr, ghead, ldg, legal);
-    else
-      hipLaunchKernelGGL(sampled_head_grad_kernel, dim3(cdiv(B, 128)), dim3(128), 0, s,
-                         a->logits, a->ld_logits, B, L.A, seed, row0, ctr, ghead, ldg);
+    launch_sampled_head_grad(a->logits, a->ld_logits, B, L.A, seed, row0, ctr, ghead, ldg, legal, s);
     rc = dx_chain<C3>(L, P, B, a, bw, ghead, ldg, s, prep, g1_fits ? part : nullptr, &g1_done, dxs);
     if (rc) return rc;
   } else {
@@ -649,8 +631,7 @@ static int backward_stacked_impl(const Layout& L, const float* P, const uint8_t*
   float* ghead = wss + kBandScratch;
   float* part_s = wss + stats_prefix_floats(B, L.A);
   const long long cap_s = wss_cap - stats_prefix_floats(B, L.A);
-  hipLaunchKernelGGL(sampled_head_grad_kernel, dim3(cdiv(B, 128)), dim3(128), 0, s, a->logits, a->ld_logits, B, L.A,
-                     seed, row0, ctr, ghead, ldg);
+  launch_sampled_head_grad(a->logits, a->ld_logits, B, L.A, seed, row0, ctr, ghead, ldg, nullptr, s);
   rc = dx_chain_pre<C3>(L, P, B, a, bws, ghead, ldg, s, prep, dxs);
   if (rc) return rc;
   const bool g1_fits = (long long)convt2_gram_blocks(B) * 33 * 32 <= cap_s;

@@ -15,13 +15,12 @@ namespace acmi {
 // row_offset: global row index of local row 0 (a batch sampled in pieces draws
 // the same uniforms as in one launch)
 // ctr_dev (nullable): device counter base added to ctr (graph-replayed rollouts)
-// MASKED (the *_masked kernels below): legal[m] is row m's legal-action word
-// (stepper.hpp legal_at); the unmasked kernels are the MASKED = false bodies.
+// MASKED: legal[m] is row m's legal-action word (stepper.hpp legal_at); the
+// unmasked instantiations take legal = nullptr and never read it.
 template <bool MASKED>
-__device__ __forceinline__ void sample_body(const float* logits, int ld, int B, int A, uint32_t seed,
-                                            uint32_t sid, uint32_t ctr, const uint32_t* ctr_dev,
-                                            uint32_t row_offset, const float* uniforms, int mode,
-                                            int32_t* actions, int32_t* bad, const uint32_t* legal) {
+__global__ void sample_kernel(const float* logits, int ld, int B, int A, uint32_t seed, uint32_t sid, uint32_t ctr,
+                              const uint32_t* ctr_dev, uint32_t row_offset, const float* uniforms, int mode,
+                              int32_t* actions, int32_t* bad, const uint32_t* legal) {
   const int m = blockIdx.x * blockDim.x + threadIdx.x;
   if (m >= B) return;
   if (ctr_dev) ctr += *ctr_dev;
@@ -32,31 +31,14 @@ __device__ __forceinline__ void sample_body(const float* logits, int ld, int B, 
   if (bad_row) atomicAdd(bad, 1);
   actions[m] = y;
 }
-__global__ void sample_kernel(const float* logits, int ld, int B, int A, uint32_t seed,
-                              uint32_t sid, uint32_t ctr, const uint32_t* ctr_dev,
-                              uint32_t row_offset, const float* uniforms, int mode,
-                              int32_t* actions, int32_t* bad) {
-  sample_body<false>(logits, ld, B, A, seed, sid, ctr, ctr_dev, row_offset, uniforms, mode, actions, bad, nullptr);
-}
-__global__ void sample_masked_kernel(const float* logits, int ld, int B, int A, uint32_t seed,
-                                     uint32_t sid, uint32_t ctr, const uint32_t* ctr_dev,
-                                     uint32_t row_offset, const float* uniforms, int mode,
-                                     int32_t* actions, int32_t* bad, const uint32_t* legal) {
-  sample_body<true>(logits, ld, B, A, seed, sid, ctr, ctr_dev, row_offset, uniforms, mode, actions, bad, legal);
-}
 
 // A row's log-sum-exp and entropy over its legal set S (all of 0..A-1 unmasked):
 //   mx = max_S z, se = sum_S expf(z - mx), lse = mx + logf(se), H = -sum_S p log p
 // in ascending a -- the one statement of the arithmetic every loss kernel shares.
 template <bool MASKED>
 __device__ __forceinline__ float row_lse(const float* z, int A, uint32_t lg) {
-  float mx = -INFINITY;
-  for (int a = 0; a < A; ++a)
-    if (legal_at<MASKED>(lg, a)) mx = fmaxf(mx, z[a]);
-  float se = 0.f;
-  for (int a = 0; a < A; ++a)
-    if (legal_at<MASKED>(lg, a)) se += expf(z[a] - mx);
-  return mx + logf(se);
+  const RowMaxSum ms = row_max_sum<MASKED>(z, A, lg);
+  return ms.mx + logf(ms.se);
 }
 template <bool MASKED>
 __device__ __forceinline__ float row_entropy(const float* z, int A, uint32_t lg, float lse) {
@@ -78,9 +60,8 @@ __device__ __forceinline__ bool action_ok(uint32_t lg, int act, int A) {
 // per-row entropy and log pi(a) (Categorical.entropy / log_prob, policies.py:87-89)
 // MASKED: over S; log pi of an action outside S is -inf (an empty S: H = 0)
 template <bool MASKED>
-__device__ __forceinline__ void categorical_body(const float* logits, int ld, int B, int A,
-                                                 const int32_t* actions, float* ent, float* lpa,
-                                                 const uint32_t* legal) {
+__global__ void categorical_kernel(const float* logits, int ld, int B, int A, const int32_t* actions, float* ent,
+                                   float* lpa, const uint32_t* legal) {
   const int m = blockIdx.x * blockDim.x + threadIdx.x;
   if (m >= B) return;
   const float* z = logits + (long long)m * ld;
@@ -92,26 +73,18 @@ __device__ __forceinline__ void categorical_body(const float* logits, int ld, in
     lpa[m] = action_ok<MASKED>(lg, act, A) ? z[act] - lse : -INFINITY;
   }
 }
-__global__ void categorical_kernel(const float* logits, int ld, int B, int A, const int32_t* actions,
-                                   float* ent, float* lpa) {
-  categorical_body<false>(logits, ld, B, A, actions, ent, lpa, nullptr);
-}
-__global__ void categorical_masked_kernel(const float* logits, int ld, int B, int A, const int32_t* actions,
-                                          float* ent, float* lpa, const uint32_t* legal) {
-  categorical_body<true>(logits, ld, B, A, actions, ent, lpa, legal);
-}
 
 // ---------------------------------------------------------------------------
-// n-step targets (objectives.py:178-214), one thread per env, reverse-free:
+// n-step targets (objectives.py:178-214), one thread per (env, step), reverse-free:
 // target[t] = sum_{i=t..stop} r_i * gp[i-t]  (ascending i, mul+add, no FMA)
 // ---------------------------------------------------------------------------
 // TRUNC (acmi_returns_trunc): a terminal flagged in tr still ends the sum but keeps a
-// bootstrap, from the value of the step after it (the lazy auto-reset's observation)
+// bootstrap, from the value of the step after it (the lazy auto-reset's observation);
+// the TRUNC = false instantiation takes tr = nullptr and never reads it
 template <bool TRUNC>
-__device__ __forceinline__ void returns_body(const float* r, const uint8_t* d, const uint8_t* tr, const float* v,
-                                             const float* vb, int N, int T, const float* gp, const float* bp,
-                                             float* tgt, float* adv) {
-  // one thread per (env, step): the first terminal at or after t ends the sum
+__global__ void returns_kernel(const float* r, const uint8_t* d, const uint8_t* tr, const float* v, const float* vb,
+                               int N, int T, const float* gp, const float* bp, float* tgt, float* adv) {
+  // the first terminal at or after t ends the sum
   const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= (long long)N * T) return;
   const int n = (int)(idx / T), t = (int)(idx - (long long)n * T);
@@ -134,16 +107,6 @@ __device__ __forceinline__ void returns_body(const float* r, const uint8_t* d, c
   tgt[idx] = target;
   adv[idx] = __fsub_rn(target, v[idx]);
 }
-__global__ void returns_kernel(const float* r, const uint8_t* d, const float* v,
-                               const float* vb, int N, int T, const float* gp,
-                               const float* bp, float* tgt, float* adv) {
-  returns_body<false>(r, d, nullptr, v, vb, N, T, gp, bp, tgt, adv);
-}
-__global__ void returns_trunc_kernel(const float* r, const uint8_t* d, const uint8_t* tr, const float* v,
-                                     const float* vb, int N, int T, const float* gp, const float* bp, float* tgt,
-                                     float* adv) {
-  returns_body<true>(r, d, tr, v, vb, N, T, gp, bp, tgt, adv);
-}
 
 // ---------------------------------------------------------------------------
 // GAE(lambda) targets (Schulman et al. 2016; an option beyond the reference,
@@ -157,9 +120,8 @@ __global__ void returns_trunc_kernel(const float* r, const uint8_t* d, const uin
 // TRUNC (acmi_gae_trunc): boot = live || truncated_t keeps gamma V_{t+1} in delta_t at
 // a truncated terminal; the lambda chain is cut at every terminal all the same
 template <bool TRUNC>
-__device__ __forceinline__ void gae_body(const float* r, const uint8_t* d, const uint8_t* tr, const float* v,
-                                         const float* vb, int N, int T, float gamma, float gl, float* tgt,
-                                         float* adv) {
+__global__ void gae_kernel(const float* r, const uint8_t* d, const uint8_t* tr, const float* v, const float* vb,
+                           int N, int T, float gamma, float gl, float* tgt, float* adv) {
   const int n = blockIdx.x * blockDim.x + threadIdx.x;
   if (n >= N) return;
   float next_v = vb[n], last = 0.f;
@@ -175,14 +137,6 @@ __device__ __forceinline__ void gae_body(const float* r, const uint8_t* d, const
     tgt[i] = __fadd_rn(last, vi);
     next_v = vi;
   }
-}
-__global__ void gae_kernel(const float* r, const uint8_t* d, const float* v, const float* vb, int N,
-                           int T, float gamma, float gl, float* tgt, float* adv) {
-  gae_body<false>(r, d, nullptr, v, vb, N, T, gamma, gl, tgt, adv);
-}
-__global__ void gae_trunc_kernel(const float* r, const uint8_t* d, const uint8_t* tr, const float* v,
-                                 const float* vb, int N, int T, float gamma, float gl, float* tgt, float* adv) {
-  gae_body<true>(r, d, tr, v, vb, N, T, gamma, gl, tgt, adv);
 }
 
 // ---------------------------------------------------------------------------
@@ -228,23 +182,73 @@ __global__ void adv_normalize_kernel(float* a, long long M, const double* mom, d
 }
 
 // ---------------------------------------------------------------------------
-// A2C loss + head gradients (objectives.py:123-154, :78)
+// A2C and PPO losses + head gradients: one thread per row, the row's policy
+// arithmetic and the block's sums stated once for both
 // ---------------------------------------------------------------------------
 constexpr int LOSS_BLOCK = 256;
+constexpr int A2C_SUMS = 3;  // policy term, entropy, value loss
+constexpr int PPO_SUMS = 5;  // surrogate, entropy, value loss, old_logp - logp, clipped rows
 
+// The policy part of a good row: lse and H over S, lpa = log pi(act), and the columns
+//   g[k] = dL/dz_k = -inv [w (onehot_k - p_k) - beta p_k (log p_k + H)]  on S, +0 outside it.
+// weight(lpa) gives w, the policy term's weight (A2C: adv; PPO: r adv where the
+// unclipped term is active, r = exp(lpa - old_logp)); with w = adv, PPO's columns
+// are A2C's bit for bit because they are these statements.
+struct RowPolicy {
+  float lse, H, lpa;
+};
+template <bool MASKED, class Weight>
+__device__ __forceinline__ RowPolicy policy_row(const float* z, int A, uint32_t lg, int act, float beta, float inv,
+                                                float* g, Weight weight) {
+  RowPolicy r;
+  r.lse = row_lse<MASKED>(z, A, lg);
+  r.H = row_entropy<MASKED>(z, A, lg, r.lse);
+  r.lpa = z[act] - r.lse;
+  const float w = weight(r.lpa);
+  for (int a = 0; a < A; ++a) {
+    if (!legal_at<MASKED>(lg, a)) {
+      g[a] = 0.f;
+      continue;
+    }
+    const float lp = z[a] - r.lse;
+    const float p = expf(lp);
+    const float oh = a == act ? 1.f : 0.f;
+    g[a] = -inv * (w * (oh - p) - beta * p * (lp + r.H));
+  }
+  return r;
+}
+
+// A block's K sums into part[block][K] (every thread of the block calls it): a wave
+// butterfly, then thread k adds sum k's wave partials in ascending wave order
+template <int K>
+__device__ __forceinline__ void block_sums(float (&s)[K], float* part) {
+  __shared__ float red[K][LOSS_BLOCK / 64];
+#pragma unroll
+  for (int k = 0; k < K; ++k) s[k] = wave_sum(s[k]);
+  const int w = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0)
+#pragma unroll
+    for (int k = 0; k < K; ++k) red[k][w] = s[k];
+  __syncthreads();
+  if (threadIdx.x < K) {
+    float a = 0.f;
+    for (int i = 0; i < LOSS_BLOCK / 64; ++i) a += red[threadIdx.x][i];
+    part[blockIdx.x * K + threadIdx.x] = a;
+  }
+}
+
+// A2C (objectives.py:123-154, :78).
 // MASKED: the softmax, entropy and policy columns over S (columns outside S are
 // +0); a bad row -- S empty or the taken action outside S -- adds nothing to the
 // policy and entropy sums, gets zero policy columns, keeps its value term and
 // counts in bad_rows (nullable).
 template <bool MASKED>
-__device__ __forceinline__ void a2c_loss_body(const float* logits, int ld, const float* values,
-                                              const int32_t* actions, const float* targets,
-                                              const float* adv, int M, int A, float beta, float vcoef,
-                                              float gscale, float* dhead, int ldh, float* part,
-                                              const uint32_t* legal, int32_t* bad_rows) {
-  __shared__ float red[3][LOSS_BLOCK / 64];
+__global__ void a2c_loss_kernel(const float* logits, int ld, const float* values, const int32_t* actions,
+                                const float* targets, const float* adv, int M, int A, float beta, float vcoef,
+                                float gscale, float* dhead, int ldh, float* part, const uint32_t* legal,
+                                int32_t* bad_rows) {
   const int m = blockIdx.x * blockDim.x + threadIdx.x;
-  float s_pl = 0.f, s_h = 0.f, s_v = 0.f;
+  float s[A2C_SUMS] = {0.f, 0.f, 0.f};
   if (m < M) {
     const float* z = logits + (long long)m * ld;
     const uint32_t lg = MASKED ? legal_bits(legal[m], A) : 0xFFFFFFFFu;
@@ -252,26 +256,16 @@ __device__ __forceinline__ void a2c_loss_body(const float* logits, int ld, const
     const bool ok = action_ok<MASKED>(lg, act, A);
     const float ad = adv[m];
     const float diff = targets[m] - values[m];
-    s_v = 0.5f * diff * diff;
+    s[2] = 0.5f * diff * diff;
     // dL/dz_k = -(1/M)[adv (onehot_k - p_k) - beta p_k (log p_k + H)]
     const float inv = gscale / (float)M;
     float* g = dhead + (long long)m * ldh;
     if (ok) {
-      const float lse = row_lse<MASKED>(z, A, lg);
-      const float H = row_entropy<MASKED>(z, A, lg, lse);
-      const float lpa = z[act] - lse;
-      s_pl = ad * lpa;
-      s_h = H;
-      for (int a = 0; a < A; ++a) {
-        if (!legal_at<MASKED>(lg, a)) {
-          g[a] = 0.f;
-          continue;
-        }
-        const float lp = z[a] - lse;
-        const float p = expf(lp);
-        const float oh = a == act ? 1.f : 0.f;
-        g[a] = -inv * (ad * (oh - p) - beta * p * (lp + H));
-      }
+      const RowPolicy rp = policy_row<MASKED>(z, A, lg, act, beta, inv, g, [&](float lpa) {
+        s[0] = ad * lpa;
+        return ad;
+      });
+      s[1] = rp.H;
     } else {
       for (int a = 0; a < A; ++a) g[a] = 0.f;
       if (bad_rows) atomicAdd(bad_rows, 1);
@@ -280,89 +274,22 @@ __device__ __forceinline__ void a2c_loss_body(const float* logits, int ld, const
     g[A] = vcoef * inv * (values[m] - targets[m]);
     for (int a = A + 1; a < ldh; ++a) g[a] = 0.f;
   }
-  s_pl = wave_sum(s_pl);
-  s_h = wave_sum(s_h);
-  s_v = wave_sum(s_v);
-  const int w = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) {
-    red[0][w] = s_pl;
-    red[1][w] = s_h;
-    red[2][w] = s_v;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float a = 0.f, b = 0.f, c = 0.f;
-    for (int i = 0; i < LOSS_BLOCK / 64; ++i) {
-      a += red[0][i];
-      b += red[1][i];
-      c += red[2][i];
-    }
-    part[blockIdx.x * 3 + 0] = a;
-    part[blockIdx.x * 3 + 1] = b;
-    part[blockIdx.x * 3 + 2] = c;
-  }
+  block_sums(s, part);
 }
 
-__global__ void a2c_loss_kernel(const float* logits, int ld, const float* values,
-                                const int32_t* actions, const float* targets,
-                                const float* adv, int M, int A, float beta, float vcoef,
-                                float gscale, float* dhead, int ldh, float* part) {
-  a2c_loss_body<false>(logits, ld, values, actions, targets, adv, M, A, beta, vcoef, gscale, dhead, ldh, part,
-                       nullptr, nullptr);
-}
-__global__ void a2c_loss_masked_kernel(const float* logits, int ld, const float* values,
-                                       const int32_t* actions, const float* targets,
-                                       const float* adv, int M, int A, float beta, float vcoef,
-                                       float gscale, float* dhead, int ldh, float* part,
-                                       const uint32_t* legal, int32_t* bad_rows) {
-  a2c_loss_body<true>(logits, ld, values, actions, targets, adv, M, A, beta, vcoef, gscale, dhead, ldh, part,
-                      legal, bad_rows);
-}
-
-__global__ void a2c_loss_final_kernel(const float* part, int nb, int M, float beta,
-                                      float scale, float* out) {
-  // one wave: deterministic fixed-order sums
-  float a = 0.f, b = 0.f, c = 0.f;
-  for (int i = threadIdx.x; i < nb; i += 64) {
-    a += part[i * 3 + 0];
-    b += part[i * 3 + 1];
-    c += part[i * 3 + 2];
-  }
-  a = wave_sum(a);
-  b = wave_sum(b);
-  c = wave_sum(c);
-  if (threadIdx.x == 0) {
-    // scale = 1/world_size: the SUM all-reduce of the update buffer then leaves
-    // the global means (every rank holds M rows)
-    const float mean_pl = a / (float)M;
-    const float mean_h = b / (float)M;
-    out[0] = scale * -(mean_pl + beta * mean_h);
-    out[1] = scale * (c / (float)M);
-    out[2] = scale * mean_h;
-  }
-}
-
-// ---------------------------------------------------------------------------
-// PPO clipped-surrogate loss + head gradients (Schulman et al. 2017; beyond the
-// reference).  One thread per row like a2c_loss_kernel, whose log-sum-exp,
-// entropy and gradient expressions are repeated here operation for operation:
-// with old_logp from categorical_kernel on the same logits r is exactly 1 and
-// dhead is a2c_loss_kernel's, bit for bit.
-// ---------------------------------------------------------------------------
-constexpr int PPO_SUMS = 5;  // surrogate, entropy, value loss, old_logp - logp, clipped rows
-
-// MASKED: as a2c_loss_body; a bad row adds nothing to the surrogate, entropy,
+// PPO clipped surrogate (Schulman et al. 2017; beyond the reference): with old_logp
+// from categorical_kernel on the same logits r is exactly 1 and dhead is
+// a2c_loss_kernel's, bit for bit.
+// MASKED: as a2c_loss_kernel; a bad row adds nothing to the surrogate, entropy,
 // KL and clipped-row sums either.
 template <bool MASKED>
-__device__ __forceinline__ void ppo_loss_body(const float* logits, int ld, const float* values,
-                                              const int32_t* actions, const float* old_logp,
-                                              const float* old_values, const float* targets, const float* adv,
-                                              int M, int A, float clip_eps, float vclip, float beta,
-                                              float vcoef, float gscale, float* dhead, int ldh, float* part,
-                                              const uint32_t* legal, int32_t* bad_rows) {
-  __shared__ float red[PPO_SUMS][LOSS_BLOCK / 64];
+__global__ void ppo_loss_kernel(const float* logits, int ld, const float* values, const int32_t* actions,
+                                const float* old_logp, const float* old_values, const float* targets,
+                                const float* adv, int M, int A, float clip_eps, float vclip, float beta,
+                                float vcoef, float gscale, float* dhead, int ldh, float* part,
+                                const uint32_t* legal, int32_t* bad_rows) {
   const int m = blockIdx.x * blockDim.x + threadIdx.x;
-  float s_pl = 0.f, s_h = 0.f, s_v = 0.f, s_kl = 0.f, s_cf = 0.f;
+  float s[PPO_SUMS] = {0.f, 0.f, 0.f, 0.f, 0.f};
   if (m < M) {
     const float* z = logits + (long long)m * ld;
     const uint32_t lg = MASKED ? legal_bits(legal[m], A) : 0xFFFFFFFFu;
@@ -371,7 +298,7 @@ __device__ __forceinline__ void ppo_loss_body(const float* logits, int ld, const
     const float ad = adv[m];
     const float v = values[m], tg = targets[m];
     const float diff = tg - v;
-    s_v = 0.5f * diff * diff;
+    s[2] = 0.5f * diff * diff;
     bool val_on = true;
     if (vclip > 0.f) {
       const float vo = old_values[m];
@@ -380,8 +307,8 @@ __device__ __forceinline__ void ppo_loss_body(const float* logits, int ld, const
       if (fabsf(dv) > vclip) {
         const float dc = tg - (vo + fminf(fmaxf(dv, -vclip), vclip));
         const float sc = 0.5f * dc * dc;
-        if (sc > s_v) {
-          s_v = sc;
+        if (sc > s[2]) {
+          s[2] = sc;
           val_on = false;
         }
       }
@@ -389,31 +316,20 @@ __device__ __forceinline__ void ppo_loss_body(const float* logits, int ld, const
     const float inv = gscale / (float)M;
     float* g = dhead + (long long)m * ldh;
     if (ok) {
-      const float lse = row_lse<MASKED>(z, A, lg);
-      const float H = row_entropy<MASKED>(z, A, lg, lse);
-      const float lpa = z[act] - lse;
-      const float olp = old_logp[m];
-      const float r = expf(lpa - olp);
-      const float rc = fminf(fmaxf(r, 1.f - clip_eps), 1.f + clip_eps);
-      const float s1 = r * ad, s2 = rc * ad;
-      // the unclipped term is the active minimum (ties: r inside the range, s1 == s2)
-      const bool pol_on = s1 <= s2;
-      s_pl = pol_on ? s1 : s2;
-      s_h = H;
-      s_kl = olp - lpa;
-      s_cf = fabsf(r - 1.f) > clip_eps ? 1.f : 0.f;
       // dL/dz_k = -(1/M)[adv r (onehot_k - p_k) [unclipped] - beta p_k (log p_k + H)]
-      const float w = pol_on ? s1 : 0.f;
-      for (int a = 0; a < A; ++a) {
-        if (!legal_at<MASKED>(lg, a)) {
-          g[a] = 0.f;
-          continue;
-        }
-        const float lp = z[a] - lse;
-        const float p = expf(lp);
-        const float oh = a == act ? 1.f : 0.f;
-        g[a] = -inv * (w * (oh - p) - beta * p * (lp + H));
-      }
+      const RowPolicy rp = policy_row<MASKED>(z, A, lg, act, beta, inv, g, [&](float lpa) {
+        const float olp = old_logp[m];
+        const float r = expf(lpa - olp);
+        const float rc = fminf(fmaxf(r, 1.f - clip_eps), 1.f + clip_eps);
+        const float s1 = r * ad, s2 = rc * ad;
+        // the unclipped term is the active minimum (ties: r inside the range, s1 == s2)
+        const bool pol_on = s1 <= s2;
+        s[0] = pol_on ? s1 : s2;
+        s[3] = olp - lpa;
+        s[4] = fabsf(r - 1.f) > clip_eps ? 1.f : 0.f;
+        return pol_on ? s1 : 0.f;
+      });
+      s[1] = rp.H;
     } else {
       for (int a = 0; a < A; ++a) g[a] = 0.f;
       if (bad_rows) atomicAdd(bad_rows, 1);
@@ -423,61 +339,32 @@ __device__ __forceinline__ void ppo_loss_body(const float* logits, int ld, const
     g[A] = val_on ? gv : 0.f;
     for (int a = A + 1; a < ldh; ++a) g[a] = 0.f;
   }
-  s_pl = wave_sum(s_pl);
-  s_h = wave_sum(s_h);
-  s_v = wave_sum(s_v);
-  s_kl = wave_sum(s_kl);
-  s_cf = wave_sum(s_cf);
-  const int w = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) {
-    red[0][w] = s_pl;
-    red[1][w] = s_h;
-    red[2][w] = s_v;
-    red[3][w] = s_kl;
-    red[4][w] = s_cf;
-  }
-  __syncthreads();
-  if (threadIdx.x < PPO_SUMS) {
-    float a = 0.f;
-    for (int i = 0; i < LOSS_BLOCK / 64; ++i) a += red[threadIdx.x][i];
-    part[blockIdx.x * PPO_SUMS + threadIdx.x] = a;
-  }
+  block_sums(s, part);
 }
 
-__global__ void ppo_loss_kernel(const float* logits, int ld, const float* values,
-                                const int32_t* actions, const float* old_logp,
-                                const float* old_values, const float* targets, const float* adv,
-                                int M, int A, float clip_eps, float vclip, float beta,
-                                float vcoef, float gscale, float* dhead, int ldh, float* part) {
-  ppo_loss_body<false>(logits, ld, values, actions, old_logp, old_values, targets, adv, M, A, clip_eps, vclip, beta,
-                       vcoef, gscale, dhead, ldh, part, nullptr, nullptr);
-}
-__global__ void ppo_loss_masked_kernel(const float* logits, int ld, const float* values,
-                                       const int32_t* actions, const float* old_logp,
-                                       const float* old_values, const float* targets, const float* adv,
-                                       int M, int A, float clip_eps, float vclip, float beta,
-                                       float vcoef, float gscale, float* dhead, int ldh, float* part,
-                                       const uint32_t* legal, int32_t* bad_rows) {
-  ppo_loss_body<true>(logits, ld, values, actions, old_logp, old_values, targets, adv, M, A, clip_eps, vclip, beta,
-                      vcoef, gscale, dhead, ldh, part, legal, bad_rows);
-}
-
-__global__ void ppo_loss_final_kernel(const float* part, int nb, int M, float beta, float scale,
-                                      float* out, float* clip_frac_out) {
-  // one wave: deterministic fixed-order sums (a2c_loss_final_kernel's order)
-  float s[PPO_SUMS];
-  for (int k = 0; k < PPO_SUMS; ++k) s[k] = 0.f;
+// K = A2C_SUMS / PPO_SUMS: out[0..2] = policy loss, value loss, mean entropy; PPO
+// adds out[3] = mean(old_logp - logp) and the clipped fraction
+template <int K>
+__global__ void loss_final_kernel(const float* part, int nb, int M, float beta, float scale, float* out,
+                                  float* clip_frac_out) {
+  // one wave: deterministic fixed-order sums
+  float s[K];
+  for (int k = 0; k < K; ++k) s[k] = 0.f;
   for (int i = threadIdx.x; i < nb; i += 64)
-    for (int k = 0; k < PPO_SUMS; ++k) s[k] += part[i * PPO_SUMS + k];
-  for (int k = 0; k < PPO_SUMS; ++k) s[k] = wave_sum(s[k]);
+    for (int k = 0; k < K; ++k) s[k] += part[i * K + k];
+  for (int k = 0; k < K; ++k) s[k] = wave_sum(s[k]);
   if (threadIdx.x == 0) {
+    // scale = 1/world_size: the SUM all-reduce of the update buffer then leaves
+    // the global means (every rank holds M rows)
     const float mean_pl = s[0] / (float)M;
     const float mean_h = s[1] / (float)M;
     out[0] = scale * -(mean_pl + beta * mean_h);
     out[1] = scale * (s[2] / (float)M);
     out[2] = scale * mean_h;
-    out[3] = scale * (s[3] / (float)M);
-    if (clip_frac_out) clip_frac_out[0] = scale * (s[4] / (float)M);
+    if constexpr (K == PPO_SUMS) {
+      out[3] = scale * (s[3] / (float)M);
+      if (clip_frac_out) clip_frac_out[0] = scale * (s[4] / (float)M);
+    }
   }
 }
 
@@ -690,29 +577,30 @@ int acmi_sample_actions_at(const float* logits, int ld, int B, int A, uint32_t s
                                  uniforms, mode, actions, bad_rows, stream);
 }
 
+// The launchers below serve an unmasked / non-truncating entry point and its _masked /
+// _trunc twin: legal, bad_rows and truncated are nullable (null: the unmasked kernel),
+// name is the entry point that was called (error text).
+static int sample_launch(const char* name, const float* logits, int ld, int B, int A, uint32_t seed,
+                         uint32_t stream_id, const uint32_t* counter_dev, uint32_t counter_add, int row_offset,
+                         const float* uniforms, int mode, const uint32_t* legal, int32_t* actions,
+                         int32_t* bad_rows, acmi_stream_t stream) {
+  ACMI_REQUIRE(logits && actions && bad_rows && B >= 0 && A >= 1 && ld >= A && row_offset >= 0,
+               ACMI_ERR_ARG, "%s: bad arguments", name);
+  if (B == 0) return ACMI_OK;
+  const auto kern = legal ? sample_kernel<true> : sample_kernel<false>;
+  hipLaunchKernelGGL(kern, dim3(cdiv(B, 256)), dim3(256), 0, (hipStream_t)stream, logits, ld, B, A, seed,
+                     stream_id, counter_add, counter_dev, (uint32_t)row_offset, uniforms, mode, actions, bad_rows,
+                     legal);
+  ACMI_LAUNCH_CHECK(name);
+  return ACMI_OK;
+}
+
 int acmi_sample_actions_dev(const float* logits, int ld, int B, int A, uint32_t seed,
                             uint32_t stream_id, const uint32_t* counter_dev, uint32_t counter_add,
                             int row_offset, const float* uniforms, int mode, int32_t* actions,
                             int32_t* bad_rows, acmi_stream_t stream) {
-  ACMI_REQUIRE(logits && actions && bad_rows && B >= 0 && A >= 1 && ld >= A && row_offset >= 0,
-               ACMI_ERR_ARG, "acmi_sample_actions: bad arguments");
-  if (B == 0) return ACMI_OK;
-  hipLaunchKernelGGL(sample_kernel, dim3(cdiv(B, 256)), dim3(256), 0, (hipStream_t)stream,
-                     logits, ld, B, A, seed, stream_id, counter_add, counter_dev,
-                     (uint32_t)row_offset, uniforms, mode, actions, bad_rows);
-  ACMI_LAUNCH_CHECK("acmi_sample_actions");
-  return ACMI_OK;
-}
-
-int acmi_categorical(const float* logits, int ld, int B, int A, const int32_t* actions,
-                     float* entropy, float* log_prob, acmi_stream_t stream) {
-  ACMI_REQUIRE(logits && B >= 0 && A >= 1 && ld >= A && (entropy || log_prob) && (!log_prob || actions),
-               ACMI_ERR_ARG, "acmi_categorical: bad arguments");
-  if (B == 0) return ACMI_OK;
-  hipLaunchKernelGGL(categorical_kernel, dim3(cdiv(B, 256)), dim3(256), 0, (hipStream_t)stream, logits, ld,
-                     B, A, actions, entropy, log_prob);
-  ACMI_LAUNCH_CHECK("acmi_categorical");
-  return ACMI_OK;
+  return sample_launch("acmi_sample_actions", logits, ld, B, A, seed, stream_id, counter_dev, counter_add,
+                       row_offset, uniforms, mode, nullptr, actions, bad_rows, stream);
 }
 
 int acmi_sample_actions_masked(const float* logits, int ld, int B, int A, uint32_t seed,
@@ -720,78 +608,89 @@ int acmi_sample_actions_masked(const float* logits, int ld, int B, int A, uint32
                                int row_offset, const float* uniforms, int mode, const uint32_t* legal,
                                int32_t* actions, int32_t* bad_rows, acmi_stream_t stream) {
   ACMI_REQUIRE_MASK("acmi_sample_actions_masked", legal, A);
-  ACMI_REQUIRE(logits && actions && bad_rows && B >= 0 && A >= 1 && ld >= A && row_offset >= 0,
-               ACMI_ERR_ARG, "acmi_sample_actions_masked: bad arguments");
+  return sample_launch("acmi_sample_actions_masked", logits, ld, B, A, seed, stream_id, counter_dev, counter_add,
+                       row_offset, uniforms, mode, legal, actions, bad_rows, stream);
+}
+
+static int categorical_launch(const char* name, const float* logits, int ld, int B, int A, const int32_t* actions,
+                              const uint32_t* legal, float* entropy, float* log_prob, acmi_stream_t stream) {
+  ACMI_REQUIRE(logits && B >= 0 && A >= 1 && ld >= A && (entropy || log_prob) && (!log_prob || actions),
+               ACMI_ERR_ARG, "%s: bad arguments", name);
   if (B == 0) return ACMI_OK;
-  hipLaunchKernelGGL(sample_masked_kernel, dim3(cdiv(B, 256)), dim3(256), 0, (hipStream_t)stream,
-                     logits, ld, B, A, seed, stream_id, counter_add, counter_dev,
-                     (uint32_t)row_offset, uniforms, mode, actions, bad_rows, legal);
-  ACMI_LAUNCH_CHECK("acmi_sample_actions_masked");
+  const auto kern = legal ? categorical_kernel<true> : categorical_kernel<false>;
+  hipLaunchKernelGGL(kern, dim3(cdiv(B, 256)), dim3(256), 0, (hipStream_t)stream, logits, ld, B, A, actions,
+                     entropy, log_prob, legal);
+  ACMI_LAUNCH_CHECK(name);
   return ACMI_OK;
+}
+
+int acmi_categorical(const float* logits, int ld, int B, int A, const int32_t* actions,
+                     float* entropy, float* log_prob, acmi_stream_t stream) {
+  return categorical_launch("acmi_categorical", logits, ld, B, A, actions, nullptr, entropy, log_prob, stream);
 }
 
 int acmi_categorical_masked(const float* logits, int ld, int B, int A, const int32_t* actions,
                             const uint32_t* legal, float* entropy, float* log_prob, acmi_stream_t stream) {
   ACMI_REQUIRE_MASK("acmi_categorical_masked", legal, A);
-  ACMI_REQUIRE(logits && B >= 0 && A >= 1 && ld >= A && (entropy || log_prob) && (!log_prob || actions),
-               ACMI_ERR_ARG, "acmi_categorical_masked: bad arguments");
-  if (B == 0) return ACMI_OK;
-  hipLaunchKernelGGL(categorical_masked_kernel, dim3(cdiv(B, 256)), dim3(256), 0, (hipStream_t)stream, logits,
-                     ld, B, A, actions, entropy, log_prob, legal);
-  ACMI_LAUNCH_CHECK("acmi_categorical_masked");
+  return categorical_launch("acmi_categorical_masked", logits, ld, B, A, actions, legal, entropy, log_prob, stream);
+}
+
+static int returns_launch(const char* name, const float* rewards, const uint8_t* terminals,
+                          const uint8_t* truncated, const float* values, const float* v_boot, int N, int T,
+                          const float* gamma_pow, const float* boot_pow, float* targets, float* adv,
+                          acmi_stream_t stream) {
+  ACMI_REQUIRE(rewards && terminals && values && v_boot && gamma_pow && boot_pow && targets &&
+                   adv && N >= 0 && T >= 1,
+               ACMI_ERR_ARG, "%s: bad arguments", name);
+  if (N == 0) return ACMI_OK;
+  const auto kern = truncated ? returns_kernel<true> : returns_kernel<false>;
+  hipLaunchKernelGGL(kern, dim3(cdiv((long long)N * T, 256)), dim3(256), 0, (hipStream_t)stream, rewards,
+                     terminals, truncated, values, v_boot, N, T, gamma_pow, boot_pow, targets, adv);
+  ACMI_LAUNCH_CHECK(name);
   return ACMI_OK;
 }
 
 int acmi_returns(const float* rewards, const uint8_t* terminals, const float* values,
                  const float* v_boot, int N, int T, const float* gamma_pow,
                  const float* boot_pow, float* targets, float* adv, acmi_stream_t stream) {
-  ACMI_REQUIRE(rewards && terminals && values && v_boot && gamma_pow && boot_pow && targets &&
-                   adv && N >= 0 && T >= 1,
-               ACMI_ERR_ARG, "acmi_returns: bad arguments");
-  if (N == 0) return ACMI_OK;
-  hipLaunchKernelGGL(returns_kernel, dim3(cdiv((long long)N * T, 256)), dim3(256), 0, (hipStream_t)stream,
-                     rewards, terminals, values, v_boot, N, T, gamma_pow, boot_pow, targets,
-                     adv);
-  ACMI_LAUNCH_CHECK("acmi_returns");
-  return ACMI_OK;
-}
-
-int acmi_gae(const float* rewards, const uint8_t* terminals, const float* values, const float* v_boot,
-             int N, int T, float gamma, float lambda, float* targets, float* adv, acmi_stream_t stream) {
-  ACMI_REQUIRE(rewards && terminals && values && v_boot && targets && adv && N >= 0 && T >= 1 &&
-                   lambda >= 0.f && lambda <= 1.f,
-               ACMI_ERR_ARG, "acmi_gae: bad arguments");
-  if (N == 0) return ACMI_OK;
-  hipLaunchKernelGGL(gae_kernel, dim3(cdiv(N, 64)), dim3(64), 0, (hipStream_t)stream, rewards, terminals,
-                     values, v_boot, N, T, gamma, gamma * lambda, targets, adv);
-  ACMI_LAUNCH_CHECK("acmi_gae");
-  return ACMI_OK;
+  return returns_launch("acmi_returns", rewards, terminals, nullptr, values, v_boot, N, T, gamma_pow, boot_pow,
+                        targets, adv, stream);
 }
 
 int acmi_returns_trunc(const float* rewards, const uint8_t* terminals, const uint8_t* truncated,
                        const float* values, const float* v_boot, int N, int T, const float* gamma_pow,
                        const float* boot_pow, float* targets, float* adv, acmi_stream_t stream) {
-  ACMI_REQUIRE(rewards && terminals && truncated && values && v_boot && gamma_pow && boot_pow && targets &&
-                   adv && N >= 0 && T >= 1,
-               ACMI_ERR_ARG, "acmi_returns_trunc: bad arguments");
+  ACMI_REQUIRE(truncated, ACMI_ERR_ARG, "acmi_returns_trunc: bad arguments");
+  return returns_launch("acmi_returns_trunc", rewards, terminals, truncated, values, v_boot, N, T, gamma_pow,
+                        boot_pow, targets, adv, stream);
+}
+
+static int gae_launch(const char* name, const float* rewards, const uint8_t* terminals, const uint8_t* truncated,
+                      const float* values, const float* v_boot, int N, int T, float gamma, float lambda,
+                      float* targets, float* adv, acmi_stream_t stream) {
+  ACMI_REQUIRE(rewards && terminals && values && v_boot && targets && adv && N >= 0 && T >= 1 &&
+                   lambda >= 0.f && lambda <= 1.f,
+               ACMI_ERR_ARG, "%s: bad arguments", name);
   if (N == 0) return ACMI_OK;
-  hipLaunchKernelGGL(returns_trunc_kernel, dim3(cdiv((long long)N * T, 256)), dim3(256), 0, (hipStream_t)stream,
-                     rewards, terminals, truncated, values, v_boot, N, T, gamma_pow, boot_pow, targets, adv);
-  ACMI_LAUNCH_CHECK("acmi_returns_trunc");
+  const auto kern = truncated ? gae_kernel<true> : gae_kernel<false>;
+  hipLaunchKernelGGL(kern, dim3(cdiv(N, 64)), dim3(64), 0, (hipStream_t)stream, rewards, terminals, truncated,
+                     values, v_boot, N, T, gamma, gamma * lambda, targets, adv);
+  ACMI_LAUNCH_CHECK(name);
   return ACMI_OK;
+}
+
+int acmi_gae(const float* rewards, const uint8_t* terminals, const float* values, const float* v_boot,
+             int N, int T, float gamma, float lambda, float* targets, float* adv, acmi_stream_t stream) {
+  return gae_launch("acmi_gae", rewards, terminals, nullptr, values, v_boot, N, T, gamma, lambda, targets, adv,
+                    stream);
 }
 
 int acmi_gae_trunc(const float* rewards, const uint8_t* terminals, const uint8_t* truncated, const float* values,
                    const float* v_boot, int N, int T, float gamma, float lambda, float* targets, float* adv,
                    acmi_stream_t stream) {
-  ACMI_REQUIRE(rewards && terminals && truncated && values && v_boot && targets && adv && N >= 0 && T >= 1 &&
-                   lambda >= 0.f && lambda <= 1.f,
-               ACMI_ERR_ARG, "acmi_gae_trunc: bad arguments");
-  if (N == 0) return ACMI_OK;
-  hipLaunchKernelGGL(gae_trunc_kernel, dim3(cdiv(N, 64)), dim3(64), 0, (hipStream_t)stream, rewards, terminals,
-                     truncated, values, v_boot, N, T, gamma, gamma * lambda, targets, adv);
-  ACMI_LAUNCH_CHECK("acmi_gae_trunc");
-  return ACMI_OK;
+  ACMI_REQUIRE(truncated, ACMI_ERR_ARG, "acmi_gae_trunc: bad arguments");
+  return gae_launch("acmi_gae_trunc", rewards, terminals, truncated, values, v_boot, N, T, gamma, lambda, targets,
+                    adv, stream);
 }
 
 int64_t acmi_adv_moments_ws_doubles(int64_t M) { (void)M; return 2LL * MOM_BLOCKS; }
@@ -815,23 +714,32 @@ int acmi_adv_normalize(float* adv, int64_t M, const double* moments, double coun
   return ACMI_OK;
 }
 
-int64_t acmi_a2c_loss_ws_floats(int M) { return 3LL * cdiv(M, LOSS_BLOCK) + 16; }
+int64_t acmi_a2c_loss_ws_floats(int M) { return (long long)A2C_SUMS * cdiv(M, LOSS_BLOCK) + 16; }
+
+static int a2c_loss_launch(const char* name, const float* logits, int ld, const float* values,
+                           const int32_t* actions, const float* targets, const float* adv, int M, int A, float beta,
+                           float vcoef, float grad_scale, float* dhead, int ldh, float* ws, float* loss_out,
+                           const uint32_t* legal, int32_t* bad_rows, acmi_stream_t stream) {
+  ACMI_REQUIRE(logits && values && actions && targets && adv && dhead && ws && loss_out &&
+                   M > 0 && A >= 1 && ld >= A && ldh >= A + 1,
+               ACMI_ERR_ARG, "%s: bad arguments", name);
+  const int nb = cdiv(M, LOSS_BLOCK);
+  hipStream_t s = (hipStream_t)stream;
+  const auto kern = legal ? a2c_loss_kernel<true> : a2c_loss_kernel<false>;
+  hipLaunchKernelGGL(kern, dim3(nb), dim3(LOSS_BLOCK), 0, s, logits, ld, values, actions, targets, adv, M, A, beta,
+                     vcoef, grad_scale, dhead, ldh, ws, legal, bad_rows);
+  hipLaunchKernelGGL(loss_final_kernel<A2C_SUMS>, dim3(1), dim3(64), 0, s, ws, nb, M, beta, grad_scale, loss_out,
+                     nullptr);
+  ACMI_LAUNCH_CHECK(name);
+  return ACMI_OK;
+}
 
 int acmi_a2c_loss(const float* logits, int ld, const float* values, const int32_t* actions,
                   const float* targets, const float* adv, int M, int A, float beta, float vcoef,
                   float grad_scale, float* dhead, int ldh, float* ws, float* loss_out,
                   acmi_stream_t stream) {
-  ACMI_REQUIRE(logits && values && actions && targets && adv && dhead && ws && loss_out &&
-                   M > 0 && A >= 1 && ld >= A && ldh >= A + 1,
-               ACMI_ERR_ARG, "acmi_a2c_loss: bad arguments");
-  const int nb = cdiv(M, LOSS_BLOCK);
-  hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(a2c_loss_kernel, dim3(nb), dim3(LOSS_BLOCK), 0, s, logits, ld, values,
-                     actions, targets, adv, M, A, beta, vcoef, grad_scale, dhead, ldh, ws);
-  hipLaunchKernelGGL(a2c_loss_final_kernel, dim3(1), dim3(64), 0, s, ws, nb, M, beta,
-                     grad_scale, loss_out);
-  ACMI_LAUNCH_CHECK("acmi_a2c_loss");
-  return ACMI_OK;
+  return a2c_loss_launch("acmi_a2c_loss", logits, ld, values, actions, targets, adv, M, A, beta, vcoef, grad_scale,
+                         dhead, ldh, ws, loss_out, nullptr, nullptr, stream);
 }
 
 int acmi_a2c_loss_masked(const float* logits, int ld, const float* values, const int32_t* actions,
@@ -839,39 +747,41 @@ int acmi_a2c_loss_masked(const float* logits, int ld, const float* values, const
                          float grad_scale, float* dhead, int ldh, float* ws, float* loss_out,
                          const uint32_t* legal, int32_t* bad_rows, acmi_stream_t stream) {
   ACMI_REQUIRE_MASK("acmi_a2c_loss_masked", legal, A);
-  ACMI_REQUIRE(logits && values && actions && targets && adv && dhead && ws && loss_out &&
-                   M > 0 && A >= 1 && ld >= A && ldh >= A + 1,
-               ACMI_ERR_ARG, "acmi_a2c_loss_masked: bad arguments");
-  const int nb = cdiv(M, LOSS_BLOCK);
-  hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(a2c_loss_masked_kernel, dim3(nb), dim3(LOSS_BLOCK), 0, s, logits, ld, values,
-                     actions, targets, adv, M, A, beta, vcoef, grad_scale, dhead, ldh, ws, legal, bad_rows);
-  hipLaunchKernelGGL(a2c_loss_final_kernel, dim3(1), dim3(64), 0, s, ws, nb, M, beta,
-                     grad_scale, loss_out);
-  ACMI_LAUNCH_CHECK("acmi_a2c_loss_masked");
-  return ACMI_OK;
+  return a2c_loss_launch("acmi_a2c_loss_masked", logits, ld, values, actions, targets, adv, M, A, beta, vcoef,
+                         grad_scale, dhead, ldh, ws, loss_out, legal, bad_rows, stream);
 }
 
 int64_t acmi_ppo_loss_ws_floats(int M) { return (long long)PPO_SUMS * cdiv(M, LOSS_BLOCK) + 16; }
+
+static int ppo_loss_launch(const char* name, const float* logits, int ld, const float* values,
+                           const int32_t* actions, const float* old_logp, const float* old_values,
+                           const float* targets, const float* adv, int M, int A, float clip_eps, float vclip,
+                           float beta, float vcoef, float grad_scale, float* dhead, int ldh, float* ws,
+                           float* loss_out, float* clip_frac_out, const uint32_t* legal, int32_t* bad_rows,
+                           acmi_stream_t stream) {
+  ACMI_REQUIRE(logits && values && actions && old_logp && targets && adv && dhead && ws &&
+                   loss_out && M > 0 && A >= 1 && ld >= A && ldh >= A + 1 && clip_eps > 0.f &&
+                   (old_values || !(vclip > 0.f)),
+               ACMI_ERR_ARG, "%s: bad arguments", name);
+  const int nb = cdiv(M, LOSS_BLOCK);
+  hipStream_t s = (hipStream_t)stream;
+  const auto kern = legal ? ppo_loss_kernel<true> : ppo_loss_kernel<false>;
+  hipLaunchKernelGGL(kern, dim3(nb), dim3(LOSS_BLOCK), 0, s, logits, ld, values, actions, old_logp, old_values,
+                     targets, adv, M, A, clip_eps, vclip, beta, vcoef, grad_scale, dhead, ldh, ws, legal, bad_rows);
+  hipLaunchKernelGGL(loss_final_kernel<PPO_SUMS>, dim3(1), dim3(64), 0, s, ws, nb, M, beta, grad_scale, loss_out,
+                     clip_frac_out);
+  ACMI_LAUNCH_CHECK(name);
+  return ACMI_OK;
+}
 
 int acmi_ppo_loss(const float* logits, int ld, const float* values, const int32_t* actions,
                   const float* old_logp, const float* old_values, const float* targets,
                   const float* adv, int M, int A, float clip_eps, float vclip, float beta,
                   float vcoef, float grad_scale, float* dhead, int ldh, float* ws, float* loss_out,
                   float* clip_frac_out, acmi_stream_t stream) {
-  ACMI_REQUIRE(logits && values && actions && old_logp && targets && adv && dhead && ws &&
-                   loss_out && M > 0 && A >= 1 && ld >= A && ldh >= A + 1 && clip_eps > 0.f &&
-                   (old_values || !(vclip > 0.f)),
-               ACMI_ERR_ARG, "acmi_ppo_loss: bad arguments");
-  const int nb = cdiv(M, LOSS_BLOCK);
-  hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(ppo_loss_kernel, dim3(nb), dim3(LOSS_BLOCK), 0, s, logits, ld, values, actions,
-                     old_logp, old_values, targets, adv, M, A, clip_eps, vclip, beta, vcoef,
-                     grad_scale, dhead, ldh, ws);
-  hipLaunchKernelGGL(ppo_loss_final_kernel, dim3(1), dim3(64), 0, s, ws, nb, M, beta, grad_scale,
-                     loss_out, clip_frac_out);
-  ACMI_LAUNCH_CHECK("acmi_ppo_loss");
-  return ACMI_OK;
+  return ppo_loss_launch("acmi_ppo_loss", logits, ld, values, actions, old_logp, old_values, targets, adv, M, A,
+                         clip_eps, vclip, beta, vcoef, grad_scale, dhead, ldh, ws, loss_out, clip_frac_out, nullptr,
+                         nullptr, stream);
 }
 
 int acmi_ppo_loss_masked(const float* logits, int ld, const float* values, const int32_t* actions,
@@ -881,19 +791,9 @@ int acmi_ppo_loss_masked(const float* logits, int ld, const float* values, const
                          float* clip_frac_out, const uint32_t* legal, int32_t* bad_rows,
                          acmi_stream_t stream) {
   ACMI_REQUIRE_MASK("acmi_ppo_loss_masked", legal, A);
-  ACMI_REQUIRE(logits && values && actions && old_logp && targets && adv && dhead && ws &&
-                   loss_out && M > 0 && A >= 1 && ld >= A && ldh >= A + 1 && clip_eps > 0.f &&
-                   (old_values || !(vclip > 0.f)),
-               ACMI_ERR_ARG, "acmi_ppo_loss_masked: bad arguments");
-  const int nb = cdiv(M, LOSS_BLOCK);
-  hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(ppo_loss_masked_kernel, dim3(nb), dim3(LOSS_BLOCK), 0, s, logits, ld, values, actions,
-                     old_logp, old_values, targets, adv, M, A, clip_eps, vclip, beta, vcoef,
-                     grad_scale, dhead, ldh, ws, legal, bad_rows);
-  hipLaunchKernelGGL(ppo_loss_final_kernel, dim3(1), dim3(64), 0, s, ws, nb, M, beta, grad_scale,
-                     loss_out, clip_frac_out);
-  ACMI_LAUNCH_CHECK("acmi_ppo_loss_masked");
-  return ACMI_OK;
+  return ppo_loss_launch("acmi_ppo_loss_masked", logits, ld, values, actions, old_logp, old_values, targets, adv, M,
+                         A, clip_eps, vclip, beta, vcoef, grad_scale, dhead, ldh, ws, loss_out, clip_frac_out,
+                         legal, bad_rows, stream);
 }
 
 int acmi_gather_rows(const uint8_t* obs, int64_t img_stride, int64_t src_rows, const int32_t* index,

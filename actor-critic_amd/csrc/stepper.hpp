@@ -284,6 +284,27 @@ __device__ __forceinline__ bool legal_at(uint32_t lg, int a) {
   return true;
 }
 
+// A row's softmax pieces over its legal set S (all of 0..A-1 unmasked), each in
+// ascending a: mx = max_S z, se = sum_S expf(z - mx), last = the last member of S
+// (-1: S is empty).  The one statement of the two loops that the loss kernels'
+// row_lse (rl.hip) and the sampled head gradients (net.hip) share.
+struct RowMaxSum {
+  float mx, se;
+  int last;
+};
+template <bool MASKED>
+__device__ __forceinline__ RowMaxSum row_max_sum(const float* z, int A, uint32_t lg) {
+  RowMaxSum r{-INFINITY, 0.f, MASKED ? -1 : A - 1};
+  for (int a = 0; a < A; ++a) {
+    if (!legal_at<MASKED>(lg, a)) continue;
+    if (MASKED) r.last = a;
+    r.mx = fmaxf(r.mx, z[a]);
+  }
+  for (int a = 0; a < A; ++a)
+    if (legal_at<MASKED>(lg, a)) r.se += expf(z[a] - r.mx);
+  return r;
+}
+
 // Categorical draw over the A logits z[0..A) (inverse CDF of softmax in f32
 // with u = u01(key4(seed, sid, ctr, row)) or the given u); -1 for a row with a
 // non-finite logit (*bad_flag set).  mode: argmax.

@@ -199,6 +199,52 @@ def test_ppo_loss_reduces_to_a2c_bit_for_bit(lib, cuda):
     assert torch.equal(out2.view(torch.int32), out.view(torch.int32))
 
 
+def test_masked_ppo_loss_reduces_to_masked_a2c_bit_for_bit_past_one_block(lib, cuda):
+    """The same identity under legal-action masks, one row past the loss kernels' 256-row
+    block: random non-empty legal sets, the actions drawn under them, old_logp from
+    acmi_categorical_masked on the same logits and masks.  dhead, the baseline loss and
+    the mean entropy are acmi_a2c_loss_masked's bits, the approximate KL and the clip
+    fraction exactly 0, no row is counted as bad."""
+    M, A, ldh = 257, 18, 20
+    d = make_inputs(M, A, EPS32, VCLIP32, seed=24)
+    rng = np.random.default_rng(25)
+    S = rng.random((M, A)) < 0.5
+    S[np.arange(M), rng.integers(0, A, M)] = True  # non-empty
+    S[0], S[M - 1, :] = True, False
+    S[M - 1, A - 1] = True  # a full row, and a single-action row in the second block
+    actions = np.array([rng.choice(np.flatnonzero(S[m])) for m in range(M)], np.int32)
+    words = (S.astype(np.uint64) << np.arange(A, dtype=np.uint64)).sum(1).astype(np.uint32)
+    L, AC, legal = dev(d['logits']), dev(actions), dev(words.view(np.int32))
+    V, TG, AD, OV = (dev(d[k]) for k in ('values', 'targets', 'adv', 'old_values'))
+    bad = torch.zeros(1, dtype=torch.int32, device=cuda)
+    st = _lib.stream_handle()
+    olp = torch.zeros(M, device=cuda)
+    _lib.call('acmi_categorical_masked', _lib.ptr(L), A, M, A, _lib.ptr(AC), _lib.ptr(legal), None, _lib.ptr(olp), st)
+
+    ppo_dhead, a2c_dhead = (torch.full((M, ldh), 7.0, device=cuda) for _ in range(2))
+    ppo_out, a2c_out, cf = torch.zeros(4, device=cuda), torch.zeros(4, device=cuda), torch.ones(1, device=cuda)
+    ws = torch.zeros(lib.acmi_ppo_loss_ws_floats(M), device=cuda)
+    _lib.call('acmi_ppo_loss_masked', _lib.ptr(L), A, _lib.ptr(V), _lib.ptr(AC), _lib.ptr(olp), _lib.ptr(OV),
+              _lib.ptr(TG), _lib.ptr(AD), M, A, EPS32, 0.0, 0.01, 0.5, 1.0, _lib.ptr(ppo_dhead), ldh, _lib.ptr(ws),
+              _lib.ptr(ppo_out), _lib.ptr(cf), _lib.ptr(legal), _lib.ptr(bad), st)
+    ws2 = torch.zeros(lib.acmi_a2c_loss_ws_floats(M), device=cuda)
+    _lib.call('acmi_a2c_loss_masked', _lib.ptr(L), A, _lib.ptr(V), _lib.ptr(AC), _lib.ptr(TG), _lib.ptr(AD), M, A,
+              0.01, 0.5, 1.0, _lib.ptr(a2c_dhead), ldh, _lib.ptr(ws2), _lib.ptr(a2c_out), _lib.ptr(legal),
+              _lib.ptr(bad), st)
+    torch.cuda.synchronize()
+    assert int(bad.item()) == 0
+    assert torch.isfinite(a2c_dhead).all() and a2c_dhead[:, :A].abs().sum() > 0
+    assert torch.equal(ppo_dhead.view(torch.int32), a2c_dhead.view(torch.int32))
+    assert torch.equal(ppo_out[1:3].view(torch.int32), a2c_out[1:3].view(torch.int32))
+    assert float(ppo_out[3]) == 0.0 and float(cf) == 0.0
+    # (the policy-loss scalars differ by construction, see above: PPO's against float64 over the legal sets)
+    z = np.where(S, d['logits'].astype(np.float64), -np.inf)
+    lp = z - (z.max(1, keepdims=True) + np.log(np.exp(z - z.max(1, keepdims=True)).sum(1, keepdims=True)))
+    H = -np.where(S, np.exp(lp) * np.where(S, lp, 0.0), 0.0).sum(1)
+    ref_pl = -(d['adv'].astype(np.float64).mean() + 0.01 * H.mean())
+    assert float(ppo_out[0]) == pytest.approx(ref_pl, rel=1e-5, abs=1e-7)
+
+
 def test_ppo_loss_grad_scale_and_argument_errors(lib, cuda):
     M, A, ldh = 1000, 18, 20
     d = make_inputs(M, A, EPS32, VCLIP32, seed=23)
