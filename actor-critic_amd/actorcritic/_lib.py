@@ -170,6 +170,14 @@ _SIGS = {
     # acmi_game_step + rules and truncated (nullable) ahead of episode_rewards
     'acmi_game_step_cuts': (c_int, [ctypes.POINTER(GameState), ctypes.POINTER(GameRules), c_int, c_int, c_u32, c_vp,
                                     c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
+    # mixed batches: games (u8 per env, nullable) after the state, bad_envs (nullable) ahead of the stream
+    'acmi_game_count': (c_int, []),
+    'acmi_game_actions': (c_int, [c_int]),
+    'acmi_game_reset_mixed': (c_int, [ctypes.POINTER(GameState), c_vp, c_int, c_int, c_u32, c_vp, c_i64, c_vp,
+                                      c_vp]),
+    'acmi_game_step_mixed': (c_int, [ctypes.POINTER(GameState), c_vp, ctypes.POINTER(GameRules), c_int, c_int,
+                                     c_u32, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp,
+                                     c_vp]),
     'acmi_atari_preprocess': (c_int, [c_vp, c_i64, c_i64, c_vp, c_int, c_int, c_int, c_vp, c_i64, c_vp]),
     'acmi_atari_stack': (c_int, [c_vp, c_i64, c_i64, c_vp, c_int, c_int, c_int, c_vp, c_int, c_vp, c_vp,
                                  c_i64, c_vp]),

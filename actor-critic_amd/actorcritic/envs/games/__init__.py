@@ -1,14 +1,15 @@
 """Device games: small real games that step and render on the GPU.
 
-:class:`DeviceGameEnvs` is a batch of Catch or Breakout envs behind ``acmi_game_step``
-(csrc/games.hip): one HIP workgroup per env advances the game's integer state and
-draws the new 84x84 frame straight into the 4-frame stack, with the synthetic stepper's
+:class:`DeviceGameEnvs` is a batch of Catch or Breakout envs (or of both, env by env:
+"mixed") behind ``acmi_game_step`` (csrc/games.hip): one HIP workgroup per env advances
+the game's integer state and draws the new 84x84 frame straight into the 4-frame stack, with the synthetic stepper's
 wrapper semantics (lazy auto-reset, FrameStackWrapper, EpisodeInfoWrapper).  It
 duck-types :class:`actorcritic.envs.atari.wrappers.SyntheticAtariEnvs`, so ``MultiEnv``
 and ``MultiEnvAgent`` put it on the device rollout; the rules are those of
 :class:`actorcritic.envs.games.host.HostGame`, bit for bit.
 
-:func:`evaluate` plays whole episodes forward-only and returns their returns.
+:func:`evaluate` plays whole episodes forward-only and returns their returns;
+:func:`returns_by_game` splits those of a mixed batch by game.
 """
 
 import ctypes
@@ -20,22 +21,25 @@ from actorcritic import _lib, spaces
 from actorcritic._engine import OBS_BYTES
 from actorcritic.envs.atari.wrappers import EpisodeInfoBatch, _mask_tensor, action_mask_bits
 from actorcritic.envs.games.host import (GAME_ACTIONS, GAMES, STATE_INTS, HostGame, check_max_episode_steps,
-                                         game_id)
+                                         game_id, game_pattern)
 
-__all__ = ['DeviceGameEnvs', 'HostGame', 'evaluate', 'GAMES', 'GAME_ACTIONS']
+__all__ = ['DeviceGameEnvs', 'HostGame', 'evaluate', 'returns_by_game', 'game_pattern', 'GAMES', 'GAME_ACTIONS']
 
 MAX_ACTIONS = 64  # the layout's widest policy head
 
 
 class DeviceGameEnvs(object):
-    """A batch of one device game with frame stacking, on one GPU.
+    """A batch of device games with frame stacking, on one GPU.
 
     Args:
-        game: 'catch' or 'breakout'.
+        game: 'catch' or 'breakout' (or its id); or whatever else
+            :func:`actorcritic.envs.games.host.game_pattern` takes: a '+'-joined string such
+            as 'catch+breakout' (global env e plays names[e % len(names)]) or a sequence of
+            num_envs names or ids.  More than one distinct game makes a MIXED batch (below).
         num_envs: environments on this device.
         num_actions: size of the Discrete action space; default the game's own count
-            (catch 3, breakout 4).  A wider head (up to 64) is allowed: the actions past
-            the own set step as NOOP, and up to 32 ``legal_action_masks`` holds the own
+            (catch 3, breakout 4; mixed: the largest, 4).  A wider head (up to 64) is allowed:
+            the actions past the own set step as NOOP, and up to 32 ``legal_action_masks`` holds the own
             set as one word per env (``MultiEnvAgent(mask_actions=True)``).
         seed: game seed (an episode's start is a pure function of seed, env, episode).
         env_offset: global id of the first env (data-parallel shards use rank*num_envs).
@@ -49,6 +53,16 @@ class DeviceGameEnvs(object):
     per env beside the terminals (the rollout: ``MultiEnvAgent.last_truncations``), and the
     batched ``step()`` leaves them in ``last_truncations`` ([N] bool device tensor; None for
     envs that emit none).  ``episode_rewards`` stay whole-game totals, at a game over only.
+
+    A single-game batch, however spelled, has ``is_mixed`` False and no ``games`` tensor, and
+    steps through the entry points above.  A mixed batch steps through
+    ``acmi_game_step_mixed`` -- the same kernel, one launch, the game read per env -- and has:
+    ``games`` (names per env), ``game_ids`` (ints per env), ``games_tensor`` (device u8 [N]),
+    ``own_action_counts`` (numpy [N]); ``game`` is the '+'-joined distinct names in id order,
+    ``game_id`` None, ``num_own_actions`` the largest own count; ``legal_action_masks``
+    holds every env's own set (4-action head: catch 0b0111, breakout 0b1111).  The rules
+    apply to every env.  ``bad_envs`` (device int32 [1]) counts envs whose id the kernel
+    refused; ids are validated here, so it stays 0.
     """
 
     # acmi_rollout_step's tail hard-wires the synthetic stepper: the rollout steps
@@ -63,16 +77,27 @@ class DeviceGameEnvs(object):
         self.emits_truncations = self.episodic_life or self.max_episode_steps is not None
         self._rules = _lib.GameRules(int(self.episodic_life), self.max_episode_steps or 0)
         self.last_truncations = None
-        self.game_id = game_id(game)
-        self.game = GAMES[self.game_id]
-        self.num_own_actions = GAME_ACTIONS[self.game]
+        self.num_envs = int(num_envs)
+        self.env_offset = int(env_offset)
+        names = game_pattern(game, self.num_envs, self.env_offset)
+        distinct = sorted(set(game_id(g) for g in names))
+        self.is_mixed = len(distinct) > 1
+        if self.is_mixed:
+            self.games = names
+            self.game_ids = tuple(game_id(g) for g in names)
+            self.own_action_counts = np.array([GAME_ACTIONS[g] for g in names], np.int64)
+            self.game_id = None
+            self.game = '+'.join(GAMES[i] for i in distinct)
+            self.num_own_actions = int(self.own_action_counts.max())
+        else:
+            self.game_id = distinct[0] if distinct else game_id(game)
+            self.game = GAMES[self.game_id]
+            self.num_own_actions = GAME_ACTIONS[self.game]
         num_actions = self.num_own_actions if num_actions is None else int(num_actions)
         if not self.num_own_actions <= num_actions <= MAX_ACTIONS:
             raise ValueError('num_actions={} outside [{}, {}] for {}'.format(num_actions, self.num_own_actions,
                                                                              MAX_ACTIONS, self.game))
-        self.num_envs = int(num_envs)
         self.seed = int(seed) & 0xFFFFFFFF
-        self.env_offset = int(env_offset)
         self.device = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
         self.observation_space = spaces.Box(low=0, high=255, shape=(84, 84, 4), dtype=np.uint8)
         self.action_space = spaces.Discrete(num_actions)
@@ -87,8 +112,13 @@ class DeviceGameEnvs(object):
         self._vars = torch.zeros((N, STATE_INTS), dtype=torch.int32, device=self.device)
         self.legal_action_masks = None
         if num_actions <= _lib.MASK_MAX_ACTIONS:
-            word = action_mask_bits(range(self.num_own_actions), num_actions)
-            self.legal_action_masks = _mask_tensor([word] * N, self.device)
+            counts = self.own_action_counts if self.is_mixed else [self.num_own_actions] * N
+            self.legal_action_masks = _mask_tensor([action_mask_bits(range(int(c)), num_actions) for c in counts],
+                                                   self.device)
+        if self.is_mixed:
+            self.games_tensor = torch.tensor(self.game_ids, dtype=torch.uint8, device=self.device)
+            self.bad_envs = torch.zeros(1, dtype=torch.int32, device=self.device)
+            self._games_base, self._bad_ptr = self.games_tensor.data_ptr(), self.bad_envs.data_ptr()
         self._states = {}
         self.state = self.range_state(0)
         self._obs = torch.zeros((N, 84, 84, 4), dtype=torch.uint8, device=self.device)
@@ -102,7 +132,7 @@ class DeviceGameEnvs(object):
         if st is None:
             st = _lib.GameState(self._episode[n0:].data_ptr(), self._step[n0:].data_ptr(),
                                 self._total[n0:].data_ptr(), self._done[n0:].data_ptr(),
-                                self._vars[n0:].data_ptr(), self.game_id)
+                                self._vars[n0:].data_ptr(), 0 if self.game_id is None else self.game_id)
             self._states[n0] = st
         return st
 
@@ -111,6 +141,10 @@ class DeviceGameEnvs(object):
         return tuple(t.cpu().numpy() for t in (self._episode, self._step, self._total, self._done, self._vars))
 
     def reset_into(self, obs_ptr, stride=OBS_BYTES):
+        if self.is_mixed:
+            _lib.call('acmi_game_reset_mixed', ctypes.byref(self.state), self._games_base, self.num_envs,
+                      self.env_offset, self.seed, ctypes.c_void_p(obs_ptr), stride, self._bad_ptr, self._stream())
+            return
         _lib.call('acmi_game_reset', ctypes.byref(self.state), self.num_envs, self.env_offset, self.seed,
                   ctypes.c_void_p(obs_ptr), stride, self._stream())
 
@@ -125,6 +159,15 @@ class DeviceGameEnvs(object):
         trunc_ptr: u8 truncations, laid out as the terminals (envs with ``emits_truncations``)."""
         if not (0 <= n0 and 0 <= n and n0 + n <= self.num_envs):
             raise ValueError('envs {} .. {} outside the batch of {}'.format(n0, n0 + n - 1, self.num_envs))
+        if self.is_mixed:  # (rules {0, 0}: acmi_game_step's; the games pointer moves with the state, a byte an env)
+            if trunc_ptr is not None and not self.emits_truncations:
+                raise ValueError('these envs emit no truncations (episodic_life / max_episode_steps are off)')
+            _lib.call('acmi_game_step_mixed', ctypes.byref(self.range_state(n0)), self._games_base + n0,
+                      ctypes.byref(self._rules), n, self.env_offset + n0, self.seed, ctypes.c_void_p(actions_ptr),
+                      ctypes.c_void_p(obs_in_ptr), in_stride, ctypes.c_void_p(obs_out_ptr), out_stride,
+                      ctypes.c_void_p(rew_ptr), ctypes.c_void_p(term_ptr), ctypes.c_void_p(trunc_ptr),
+                      ctypes.c_void_p(ep_ptr), ld, self._bad_ptr, self._stream())
+            return
         if self.emits_truncations:
             _lib.call('acmi_game_step_cuts', ctypes.byref(self.range_state(n0)), ctypes.byref(self._rules), n,
                       self.env_offset + n0, self.seed, ctypes.c_void_p(actions_ptr), ctypes.c_void_p(obs_in_ptr),
@@ -177,7 +220,7 @@ def evaluate(model, envs, episodes_per_env, greedy=True, seed=0, uniform=False, 
 
     uniform: the actions are drawn uniformly from the game's own set on the host
         (np.random.RandomState(seed)) and the model is not run (it may be None): the
-        random baseline.
+        random baseline.  In a mixed batch every env draws from ITS game's own set.
     return_actions: also returns the actions taken, int32 [steps, num_envs].
     max_steps: give up (RuntimeError) after that many steps; default
         episodes_per_env * 2001 (Breakout's step cap + the reset step).
@@ -185,6 +228,12 @@ def evaluate(model, envs, episodes_per_env, greedy=True, seed=0, uniform=False, 
     ``envs`` with ``episodic_life=True`` raise ValueError: the episode count here is a count
     of terminals, and a life cut is not the end of a game.  (``max_episode_steps`` is fine:
     a truncated game is over and reports its total.)
+
+    A mixed batch (``envs.is_mixed``): the Catch envs play on past their count while the
+    Breakout envs finish (column E of the scratch takes those); :func:`returns_by_game`
+    splits the result.  A model that holds per-env legal-action masks must hold exactly
+    ``envs.legal_action_masks`` (ValueError otherwise): masks are indexed by env, and a
+    batch composed differently from the one they were made for would use the wrong sets.
     """
     if getattr(envs, 'episodic_life', False):
         raise ValueError('evaluate() counts terminals as finished games: build the evaluation envs without '
@@ -205,6 +254,14 @@ def evaluate(model, envs, episodes_per_env, greedy=True, seed=0, uniform=False, 
     taken = []
     rng = np.random.RandomState(seed) if uniform else None
     eng = None if uniform else model.engine
+    mixed = getattr(envs, 'is_mixed', False)
+    if mixed and eng is not None and eng.masks is not None:
+        own = envs.legal_action_masks
+        if own is None or own.numel() != eng.masks.numel() or \
+                not torch.equal(own.view(torch.int32).to(eng.masks.device), eng.masks):
+            raise ValueError('the model\'s legal-action masks are not those of this mixed batch ({}): masks are '
+                             'per env, so evaluate on a batch composed like the one they were set for, or clear '
+                             'them (set_action_masks(None))'.format(envs.game))
     if eng is not None:
         acts = eng.activations(N, 'evaluate')
         saved_counter = eng.sample_counter
@@ -213,7 +270,8 @@ def evaluate(model, envs, episodes_per_env, greedy=True, seed=0, uniform=False, 
     try:
         while True:
             if uniform:
-                actions.copy_(torch.from_numpy(rng.randint(0, envs.num_own_actions, size=N).astype(np.int32)))
+                high = envs.own_action_counts if mixed else envs.num_own_actions
+                actions.copy_(torch.from_numpy(rng.randint(0, high, size=N).astype(np.int32)))
             else:
                 eng.forward(obs.data_ptr(), N, acts.struct, want_value=False)
                 eng.sample_counter = steps  # (a draw is keyed by seed, stream 1 and the step)
@@ -240,4 +298,20 @@ def evaluate(model, envs, episodes_per_env, greedy=True, seed=0, uniform=False, 
     out = returns[:, :E].contiguous()
     if return_actions:
         return out, torch.stack(taken)
+    return out
+
+
+def returns_by_game(envs, returns):
+    """Splits evaluate()'s returns [num_envs, E] by game -> {name: tensor [envs of that game, E]},
+    in id order; a single-game batch gives one entry."""
+    if returns.shape[0] != envs.num_envs:
+        raise ValueError('returns of {} envs for a batch of {}'.format(returns.shape[0], envs.num_envs))
+    if not getattr(envs, 'is_mixed', False):
+        return {envs.game: returns}
+    ids = np.asarray(envs.game_ids)
+    out = {}
+    for i, name in enumerate(GAMES):
+        rows = np.nonzero(ids == i)[0]
+        if rows.size:
+            out[name] = returns[torch.as_tensor(rows, device=returns.device)]
     return out

@@ -70,6 +70,13 @@ has EpisodeInfoWrapper inside the life cut, as the reference chain does: its epi
 totals are whole-game totals at a game over.  (An EpisodeInfoWrapper put around an
 ``episodic_life=True`` HostGame on the list path sees that game's terminals and so totals
 per life.)
+
+Mixed batches.  A batch may hold both games, env by env (:func:`game_pattern`; the
+stepper's ``acmi_game_step_mixed``): it is N HostGame of different games, and nothing
+couples them.  An env's trace is a pure function of (seed, global env id, its game, its
+actions), whatever its neighbours play: the hash keys hold the game's tag, and a
+'+'-pattern assigns the game by the global env id, so a data-parallel shard plays what
+the same envs play in one large batch.
 """
 
 import numpy as np
@@ -110,6 +117,29 @@ def game_id(game):
     if game in GAMES:
         return GAMES.index(game)
     raise ValueError('unknown game {!r}: one of {}'.format(game, GAMES))
+
+
+def game_pattern(game, num_envs, env_offset=0):
+    """The game of every env of a batch -> tuple of num_envs names.
+
+    game: a name or id (every env plays it); a '+'-joined string of names such as
+    'catch+breakout', under which GLOBAL env e = env_offset + n plays names[e % len(names)]
+    (a game follows the global env id, as an episode's start does, so shards agree with
+    the whole batch); or an explicit sequence of num_envs names or ids.  ValueError for
+    anything else: an unknown name, an empty part, a wrong length."""
+    num_envs, env_offset = int(num_envs), int(env_offset)
+    if num_envs < 0 or env_offset < 0:
+        raise ValueError('num_envs and env_offset must not be negative')
+    if isinstance(game, str):
+        names = tuple(GAMES[game_id(part)] for part in game.split('+'))  # ('' raises in game_id)
+        return tuple(names[(env_offset + n) % len(names)] for n in range(num_envs))
+    if isinstance(game, (int, np.integer)):
+        return (GAMES[game_id(game)],) * num_envs
+    if isinstance(game, (list, tuple, np.ndarray)):
+        if len(game) != num_envs:
+            raise ValueError('{} games for {} envs'.format(len(game), num_envs))
+        return tuple(GAMES[game_id(g)] for g in game)
+    raise ValueError('game must be a name, an id, a \'+\'-joined string or a sequence, got {!r}'.format(game))
 
 
 def check_max_episode_steps(max_episode_steps):

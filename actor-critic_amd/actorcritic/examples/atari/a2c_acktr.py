@@ -36,6 +36,9 @@ def train_a2c_acktr(acktr, env_id, num_envs, num_steps, checkpoint_path, model_n
     ``legal_action_masks``); actions, losses and K-FAC statistics then run over the legal set.
     ``game`` (``--game catch|breakout``): a device game (envs.games.DeviceGameEnvs) instead of the
     synthetic stepper -- something that can be learned; ``env_id`` then only names the results.
+    ``--game catch+breakout`` is a mixed batch: global env e plays the (e % 2)-th name, one network and
+    one head (4 actions; with ``mask_actions`` 18 and every env's own set as its mask), and the scalar
+    log gains ``episode_reward/<game>`` beside ``episode_reward``.
     ``episodic_life`` (``--episodic-life``) and ``max_episode_steps`` (``--max-episode-steps N``), device
     games only: a lost life is a terminal for the learner, and a step cap of N (1..2000) whose terminals
     are truncations -- the targets keep their bootstrap there (``model.truncations_placeholder``).
@@ -105,7 +108,8 @@ def train_a2c_acktr(acktr, env_id, num_envs, num_steps, checkpoint_path, model_n
                     mean_episode_reward = (np.nan if np.all(np.isnan(episode_rewards))
                                            else float(np.nanmean(episode_rewards)))
                     summary_writer.add(step, policy_loss=float(out[3]), baseline_loss=float(out[4]),
-                                       policy_entropy=float(out[5]), episode_reward=mean_episode_reward)
+                                       policy_entropy=float(out[5]), episode_reward=mean_episode_reward,
+                                       **episode_rewards_by_game(multi_env.batched, episode_rewards))
                 if on_update is not None:
                     on_update(updates, model)
                 if checkpoint_path is not None and step % 100 == 0 and step > 0 and parallel.rank() == 0:
@@ -133,14 +137,29 @@ def create_environments(env_id, num_envs, seed=0, full_action_set=False):
 
 
 def create_game_environments(game, num_envs, seed=0, full_action_set=False, episodic_life=False,
-                             max_episode_steps=None):
-    """This rank's shard of a device game ('catch', 'breakout').  ``full_action_set``: under the
-    18-action head, the game's own actions in ``legal_action_masks``.  ``episodic_life`` and
-    ``max_episode_steps``: DeviceGameEnvs' (training envs only: evaluate() refuses episodic life)."""
+                             max_episode_steps=None, env_offset=None):
+    """This rank's shard of a device game ('catch', 'breakout') or of a mixed batch (a pattern such as
+    'catch+breakout': the game follows the global env id, so the shards agree with one large batch).
+    ``full_action_set``: under the 18-action head, every env's own actions in ``legal_action_masks``.
+    ``episodic_life`` and ``max_episode_steps``: DeviceGameEnvs' (training envs only: evaluate()
+    refuses episodic life).  ``env_offset``: global id of the first env, default rank * num_envs."""
     from actorcritic.envs.games import DeviceGameEnvs
+    if env_offset is None:
+        env_offset = parallel.rank() * num_envs
     return DeviceGameEnvs(game, num_envs, num_actions=18 if full_action_set else None, seed=seed,
-                          env_offset=parallel.rank() * num_envs, episodic_life=episodic_life,
-                          max_episode_steps=max_episode_steps)
+                          env_offset=env_offset, episodic_life=episodic_life, max_episode_steps=max_episode_steps)
+
+
+def episode_rewards_by_game(batched, episode_rewards):
+    """The scalar log's per-game keys of a mixed device-game batch: {'episode_reward/<game>': mean over
+    the episodes that game's envs finished in this batch (NaN: none did)}; {} for anything else."""
+    if not getattr(batched, 'is_mixed', False):
+        return {}
+    out = {}
+    for name in sorted(set(batched.games)):
+        rows = episode_rewards[np.array([g == name for g in batched.games])]
+        out['episode_reward/' + name] = np.nan if np.all(np.isnan(rows)) else float(np.nanmean(rows))
+    return out
 
 
 def create_host_environments(env_fns, subprocess=True):

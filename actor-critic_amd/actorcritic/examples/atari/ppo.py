@@ -20,6 +20,7 @@ from actorcritic import checkpoint, parallel
 from actorcritic.agents import MultiEnvAgent
 from actorcritic.envs.atari.model import AtariModel
 from actorcritic.examples.atari.a2c_acktr import (create_environments, create_game_environments,
+                                                  episode_rewards_by_game,
                                                    create_host_environments, load_model, save_model)
 from actorcritic.multi_env import MultiEnv
 from actorcritic.nn import AdamOptimizer, ClipGlobalNormOptimizer, linear_decay
@@ -42,9 +43,9 @@ def train_ppo(env_id, num_envs, num_steps, checkpoint_path, model_name, summary_
     makes a host env with raw RGB frames (a2c_acktr.create_host_environments); ``num_envs`` is
     then their number.
     ``mask_actions`` (``--mask-actions``): invalid-action masking, as in a2c_acktr.train_a2c_acktr.
-    ``game`` (``--game catch|breakout``), ``episodic_life`` (``--episodic-life``), ``max_episode_steps``
-    (``--max-episode-steps N``), ``checkpoint_path`` None and ``on_update``: as in
-    a2c_acktr.train_a2c_acktr.
+    ``game`` (``--game catch|breakout``, or a mixed batch: ``catch+breakout``), ``episodic_life``
+    (``--episodic-life``), ``max_episode_steps`` (``--max-episode-steps N``), ``checkpoint_path`` None and
+    ``on_update``: as in a2c_acktr.train_a2c_acktr.
     """
     parallel.init_from_env()
     if game is None and (episodic_life or max_episode_steps is not None):
@@ -110,7 +111,8 @@ def train_ppo(env_id, num_envs, num_steps, checkpoint_path, model_name, summary_
                                            else float(np.nanmean(episode_rewards)))
                     summary_writer.add(step, policy_loss=float(out[3]), baseline_loss=float(out[4]),
                                        policy_entropy=float(out[5]), approx_kl=float(out[6]),
-                                       clip_fraction=float(out[7]), episode_reward=mean_episode_reward)
+                                       clip_fraction=float(out[7]), episode_reward=mean_episode_reward,
+                                       **episode_rewards_by_game(multi_env.batched, episode_rewards))
                 if on_update is not None:
                     on_update(updates, model)
                 if checkpoint_path is not None and step % 100 == 0 and step > 0 and parallel.rank() == 0:

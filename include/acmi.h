@@ -647,6 +647,36 @@ int acmi_game_step_cuts(const acmi_game_state_t* st, const acmi_game_rules_t* ru
                         uint8_t* truncated, float* episode_rewards, int64_t ld,
                         acmi_stream_t stream);
 
+/* Mixed batches: Catch and Breakout envs side by side in one launch, under one
+ * policy head (the envs' own action sets as per-env legal-action words: catch
+ * 0b0111, breakout 0b1111; actorcritic.envs.games: DeviceGameEnvs('catch+breakout')).
+ * acmi_game_count() is 2; acmi_game_actions(game) is a game's own action count (3, 4;
+ * ACMI_ERR_ARG for another id).
+ * games: one byte per env OF THE CALL (device; the pointer already at the call's first
+ * env, as the state pointers are): env n plays games[n], whatever st->game says (which
+ * must still be a valid id).  games == NULL: st->game for every env; then
+ * acmi_game_reset_mixed is acmi_game_reset and acmi_game_step_mixed is
+ * acmi_game_step_cuts, byte for byte (the same two kernels).  rules is required, as in
+ * acmi_game_step_cuts, and holds for every env; {0, 0} gives acmi_game_step's behaviour.
+ * An env's trace is a function of (seed, env_offset + n, its game, its actions) only.
+ * An id at or past acmi_game_count() makes a BAD env: its state is left untouched, its
+ * output stack zero-filled, reward 0, terminal 0, truncated 0, episode reward the quiet
+ * NaN, and it is counted once per call in bad_envs (device int32, nullable,
+ * accumulates; the caller zeroes it).
+ * Argument errors are ACMI_ERR_ARG with nothing enqueued, as above. */
+int acmi_game_count(void);
+int acmi_game_actions(int game);
+int acmi_game_reset_mixed(const acmi_game_state_t* st, const uint8_t* games, int N,
+                          int env_offset, uint32_t seed, uint8_t* obs_out,
+                          int64_t out_stride, int32_t* bad_envs, acmi_stream_t stream);
+int acmi_game_step_mixed(const acmi_game_state_t* st, const uint8_t* games,
+                         const acmi_game_rules_t* rules, int N, int env_offset,
+                         uint32_t seed, const int32_t* actions, const uint8_t* obs_in,
+                         int64_t in_stride, uint8_t* obs_out, int64_t out_stride,
+                         float* rewards, uint8_t* terminals, uint8_t* truncated,
+                         float* episode_rewards, int64_t ld, int32_t* bad_envs,
+                         acmi_stream_t stream);
+
 /* ------------------------------------------------------------------------
  * Atari frame preprocessing for real (raw RGB) frames, batched over envs:
  * replaces the frame half of the reference's per-env wrapper chain

@@ -6,7 +6,9 @@
          launches, the cases in alternating rounds; us per launch and the GB/s of the
          stack traffic (2 * 28224 * N bytes a launch, computed from the shape).
          catch-cuts / breakout-cuts: acmi_game_step_cuts with every option on (episodic
-         life, a step cap, the truncated array written).
+         life, a step cap, the truncated array written).  mixed: acmi_game_step_mixed on a
+         50/50 batch (catch+breakout, env by env), to be read against the mean of the two
+         single-game timings of the same process.
   iter   the unfused 32 x 5 A2C iteration (rollout + update, a host clock around a device
          synchronise) on catch against the synthetic stepper forced onto the same
          unfused path (ACMI_ROLLOUT_FUSED=0), and the synthetic stepper's default
@@ -41,6 +43,8 @@ def cmd_step(args):
     if not args.no_cuts:
         for g in ('catch', 'breakout'):
             envs[g + '-cuts'] = DeviceGameEnvs(g, N, seed=1, episodic_life=True, max_episode_steps=1000)
+    if not args.no_mixed:
+        envs['mixed'] = DeviceGameEnvs('catch+breakout', N, seed=1)
     if args.cases:
         envs = {k: envs[k] for k in args.cases}
     trunc = torch.zeros(N, dtype=torch.uint8, device=dev)
@@ -131,10 +135,12 @@ def main():
     st.add_argument('--calls', type=int, default=500)
     st.add_argument('--rounds', type=int, default=3)
     st.add_argument('--cases', nargs='+', default=None,
-                    help='only these cases (synthetic, catch, breakout, catch-cuts, breakout-cuts): a kernel '
+                    help='only these cases (synthetic, catch, breakout, catch-cuts, breakout-cuts, mixed): a kernel '
                          'trace of one case per process tells the kernels of the two entry points apart')
     st.add_argument('--no-cuts', action='store_true',
                     help='leave the -cuts cases out (an older libacmi under ACMI_LIB has no acmi_game_step_cuts)')
+    st.add_argument('--no-mixed', action='store_true',
+                    help='leave the mixed case out (an older libacmi under ACMI_LIB has no acmi_game_step_mixed)')
     st.set_defaults(fn=cmd_step)
     it = sub.add_parser('iter')
     it.add_argument('--env', choices=('catch', 'synthetic-unfused', 'synthetic'), default='catch')

@@ -11,6 +11,12 @@ return, after a first line with the uniform policy's.  The lines also go to --ou
 --episodic-life and --max-episode-steps N train under those rules (DeviceGameEnvs); the
 evaluation envs never take episodic life (evaluate counts terminals as finished games), so
 returns stay whole-game returns and compare across the settings.
+
+--game catch+breakout trains on the mixed batch (global env e plays the (e % 2)-th name, one
+4-action head) and evaluates PER GAME, on single-game batches that the training never saw:
+one line per game and point, with "eval_game".  --mask-actions: the 18-action head with every
+env's own set as its legal-action mask (for the evaluation the model's mask words are
+overwritten in place with the evaluation batch's and put back, so --eval-envs must be --envs).
 """
 import argparse
 import json
@@ -26,46 +32,66 @@ def run(args, seed, emit):
     import torch
     assert torch.cuda.is_available(), 'no GPU: nothing is learned without one'
     from actorcritic import session as sess
-    from actorcritic.envs.games import DeviceGameEnvs, evaluate
+    from actorcritic.envs.games import GAMES, DeviceGameEnvs, evaluate
     from actorcritic.examples.atari.a2c_acktr import train_a2c_acktr
     from actorcritic.examples.atari.ppo import train_ppo
     torch.cuda.set_device(0)
     sess.reset_default_graph()
     N, T, E = args.envs, args.steps, args.episodes
     head = dict(algo=args.algo, game=args.game, seed=seed, envs=N, steps=T, eval_envs=args.eval_envs, eval_episodes=E,
-                episodic_life=args.episodic_life, max_episode_steps=args.max_episode_steps)
+                episodic_life=args.episodic_life, max_episode_steps=args.max_episode_steps,
+                mask_actions=args.mask_actions)
+    eval_games = [g for g in GAMES if g in args.game.split('+')]
+    mixed = len(eval_games) > 1
+    # the head of the trained model: the mixed batch's (4) or the full set under masks (18)
+    num_actions = 18 if args.mask_actions else (4 if mixed else None)
+    episodes = lambda g: args.breakout_episodes if (mixed and g == 'breakout') else E
     rules = dict(episodic_life=args.episodic_life, max_episode_steps=args.max_episode_steps)
 
     def stats(returns):
         r = returns.double().flatten()
         return dict(mean_return=round(float(r.mean()), 4), var=round(float(r.var(unbiased=True)), 4), n=r.numel())
 
-    eval_envs = lambda: DeviceGameEnvs(args.game, args.eval_envs, seed=1000 + seed,
-                                       max_episode_steps=args.max_episode_steps)
-    emit(dict(head, policy='uniform', updates=0, env_steps=0, **stats(evaluate(None, eval_envs(), E, uniform=True,
-                                                                                 seed=seed))))
+    eval_envs = lambda g: DeviceGameEnvs(g, args.eval_envs, num_actions=num_actions, seed=1000 + seed,
+                                         max_episode_steps=args.max_episode_steps)
+    tag = lambda g: dict(eval_game=g) if mixed else {}
+    for g in eval_games:
+        emit(dict(head, policy='uniform', updates=0, env_steps=0, **tag(g),
+                  **stats(evaluate(None, eval_envs(g), episodes(g), uniform=True, seed=seed))))
     t0 = time.perf_counter()
+
+    def play(model, g):
+        envs = eval_envs(g)
+        words = model.engine.masks
+        if words is None:
+            return evaluate(model, envs, episodes(g), greedy=not args.sample, seed=seed)
+        saved = words.clone()  # in place: a captured rollout keeps reading this tensor
+        words.copy_(envs.legal_action_masks.view(torch.int32))
+        try:
+            return evaluate(model, envs, episodes(g), greedy=not args.sample, seed=seed)
+        finally:
+            words.copy_(saved)
 
     def on_update(updates, model):
         if updates % args.every == 0 or updates == args.updates:
             torch.cuda.synchronize()
             train_s = time.perf_counter() - t0
-            emit(dict(head, policy='sampled' if args.sample else 'greedy', updates=updates,
-                      env_steps=updates * N * T, wall_s=round(train_s, 2),
-                      **stats(evaluate(model, eval_envs(), E, greedy=not args.sample, seed=seed))))
+            for g in eval_games:
+                emit(dict(head, policy='sampled' if args.sample else 'greedy', updates=updates,
+                          env_steps=updates * N * T, wall_s=round(train_s, 2), **tag(g), **stats(play(model, g))))
 
     if args.algo == 'ppo':
         train_ppo(args.game, N, T, None, args.game, max_updates=args.updates, seed=seed, game=args.game,
-                  on_update=on_update, **rules)
+                  on_update=on_update, mask_actions=args.mask_actions, **rules)
     else:
         train_a2c_acktr(args.algo == 'acktr', args.game, N, T, None, args.game, max_updates=args.updates, seed=seed,
-                        game=args.game, on_update=on_update, **rules)
+                        game=args.game, on_update=on_update, mask_actions=args.mask_actions, **rules)
 
 
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument('--algo', choices=('a2c', 'acktr', 'ppo'), default='a2c')
-    ap.add_argument('--game', choices=('catch', 'breakout'), default='catch')
+    ap.add_argument('--game', choices=('catch', 'breakout', 'catch+breakout'), default='catch')
     ap.add_argument('--envs', type=int, default=32)
     ap.add_argument('--steps', type=int, default=None, help='rollout length (default: a2c 5, acktr 20, ppo 128)')
     ap.add_argument('--updates', type=int, default=2000)
@@ -73,11 +99,16 @@ def main():
     ap.add_argument('--seeds', type=int, nargs='+', default=[1])
     ap.add_argument('--eval-envs', type=int, default=32)
     ap.add_argument('--episodes', type=int, default=8, help='evaluation episodes per env')
+    ap.add_argument('--breakout-episodes', type=int, default=2,
+                    help='evaluation episodes per Breakout env of a mixed run (its episodes are long)')
+    ap.add_argument('--mask-actions', action='store_true', help='18-action head, own sets as legal-action masks')
     ap.add_argument('--sample', action='store_true', help='evaluate draws from the policy instead of its mode')
     ap.add_argument('--episodic-life', action='store_true', help='train with a lost life as a terminal')
     ap.add_argument('--max-episode-steps', type=int, default=None, help='step cap (truncation), 1..2000')
     ap.add_argument('--out', default=None, help='also append the JSON lines to this file')
     args = ap.parse_args()
+    if args.mask_actions and args.eval_envs != args.envs:
+        ap.error('--mask-actions needs --eval-envs equal to --envs (one mask word per env)')
     if args.steps is None:
         args.steps = {'a2c': 5, 'acktr': 20, 'ppo': 128}[args.algo]  # the examples' rollout lengths
     out = open(args.out, 'a') if args.out else None
