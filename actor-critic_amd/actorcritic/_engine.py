@@ -152,6 +152,13 @@ class UpdateState(object):
         self.fwd = None
         self.loss_reduced = True  # loss slots hold global means (see objectives._Loss)
         self._side = None
+        self.norm_rewards = None  # the scaled rewards (objectives' normalize_returns), made on first use
+
+    def reward_buffer(self, N, T):
+        """[N][T] f32 for the scaled rewards the targets read in place of the fed ones."""
+        if self.norm_rewards is None:
+            self.norm_rewards = torch.zeros(self.M, dtype=torch.float32, device=self.targets.device)
+        return self.norm_rewards.view(N, T)
 
     def side(self, eng):
         """Second backward workspace (d1..d4, dhead, ws) and a side stream: the sampled-

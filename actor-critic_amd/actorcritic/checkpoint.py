@@ -40,11 +40,24 @@ def _optimizer_state(optimizer):
     return out
 
 
-def save(prefix, step, model, optimizer=None):
+def _normalizer(objective):
+    """The objective's ReturnNormalizer (normalize_returns=), or None."""
+    return getattr(objective, 'return_normalizer', None)
+
+
+def save(prefix, step, model, optimizer=None, objective=None):
+    """``objective``: with a ReturnNormalizer its stats and settings are stored under retnorm/
+    (not the envs' running returns: env state is not checkpointed)."""
     path = '{}-{}.pt'.format(prefix, int(step))
     blob = {'params': model.params.detach().cpu(), 'global_step': torch.tensor(int(step)),
             'num_actions': torch.tensor(model.num_actions), 'conv3_filters': torch.tensor(model.conv3_num_filters)}
     blob.update(_optimizer_state(optimizer))
+    norm = _normalizer(objective)
+    if norm is not None:
+        st = norm.state_dict()
+        blob['retnorm/stats'] = st['stats']
+        blob['retnorm/epsilon'] = torch.tensor(st['epsilon'], dtype=torch.float64)
+        blob['retnorm/clip'] = torch.tensor(st['clip'], dtype=torch.float64)
     tmp = path + '.tmp'
     torch.save(blob, tmp)
     os.replace(tmp, path)
@@ -63,7 +76,9 @@ def latest(directory):
     return path if os.path.exists(path) else None
 
 
-def load(path, model, optimizer=None, global_step=None):
+def load(path, model, optimizer=None, global_step=None, objective=None):
+    """``objective``: its ReturnNormalizer takes the retnorm/ entries when the file has them
+    (a checkpoint written without them leaves it as it is)."""
     blob = torch.load(path, map_location='cpu', weights_only=True)
     if int(blob['num_actions']) != model.num_actions or int(blob['conv3_filters']) != model.conv3_num_filters:
         raise ValueError('checkpoint was written for a different model')
@@ -85,6 +100,10 @@ def load(path, model, optimizer=None, global_step=None):
             for attr in ('cov_updates', 'inverse_updates'):
                 if 'kfac_meta/' + attr in blob:
                     setattr(optimizer, attr, int(blob['kfac_meta/' + attr]))
+    norm = _normalizer(objective)
+    if norm is not None and 'retnorm/stats' in blob:
+        norm.load_state_dict({'stats': blob['retnorm/stats'], 'epsilon': float(blob['retnorm/epsilon']),
+                              'clip': float(blob['retnorm/clip'])})
     return blob
 
 

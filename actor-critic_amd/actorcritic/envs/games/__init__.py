@@ -21,7 +21,7 @@ from actorcritic import _lib, spaces
 from actorcritic._engine import OBS_BYTES
 from actorcritic.envs.atari.wrappers import EpisodeInfoBatch, _mask_tensor, action_mask_bits
 from actorcritic.envs.games.host import (GAME_ACTIONS, GAMES, STATE_INTS, HostGame, check_max_episode_steps,
-                                         game_id, game_pattern)
+                                         env_game_ids, game_id, game_pattern)
 
 __all__ = ['DeviceGameEnvs', 'HostGame', 'evaluate', 'returns_by_game', 'game_pattern', 'GAMES', 'GAME_ACTIONS']
 
@@ -80,11 +80,13 @@ class DeviceGameEnvs(object):
         self.num_envs = int(num_envs)
         self.env_offset = int(env_offset)
         names = game_pattern(game, self.num_envs, self.env_offset)
-        distinct = sorted(set(game_id(g) for g in names))
+        # every env's id, mixed or not (a per-game ReturnNormalizer's groups: return_norm.groups_for_envs)
+        self.env_game_ids = env_game_ids(game, self.num_envs, self.env_offset)
+        distinct = sorted(set(self.env_game_ids))
         self.is_mixed = len(distinct) > 1
         if self.is_mixed:
             self.games = names
-            self.game_ids = tuple(game_id(g) for g in names)
+            self.game_ids = self.env_game_ids
             self.own_action_counts = np.array([GAME_ACTIONS[g] for g in names], np.int64)
             self.game_id = None
             self.game = '+'.join(GAMES[i] for i in distinct)

@@ -142,6 +142,12 @@ def game_pattern(game, num_envs, env_offset=0):
     raise ValueError('game must be a name, an id, a \'+\'-joined string or a sequence, got {!r}'.format(game))
 
 
+def env_game_ids(game, num_envs, env_offset=0):
+    """The game id of every env of a batch (game_pattern's arguments) -> tuple of num_envs ints:
+    what DeviceGameEnvs steps by, and the groups of a per-game ReturnNormalizer."""
+    return tuple(game_id(g) for g in game_pattern(game, num_envs, env_offset))
+
+
 def check_max_episode_steps(max_episode_steps):
     """None (the game's own cap) or an int in 1..2000; ValueError otherwise."""
     if max_episode_steps is None:

@@ -19,12 +19,13 @@ from actorcritic.kfac_utils import ColdStartPeriodicInvUpdateKfacOpt, LayerColle
 from actorcritic.multi_env import MultiEnv
 from actorcritic.nn import ClipGlobalNormOptimizer, MomentumOptimizer, RMSPropOptimizer, linear_decay
 from actorcritic.objectives import A2CObjective
+from actorcritic.return_norm import ReturnNormalizer
 from actorcritic.session import Session, get_or_create_global_step, no_op
 
 
 def train_a2c_acktr(acktr, env_id, num_envs, num_steps, checkpoint_path, model_name, summary_path=None,
                     max_updates=None, seed=0, log_every=10, env_fns=None, mask_actions=False, game=None,
-                    on_update=None, episodic_life=False, max_episode_steps=None):
+                    on_update=None, episodic_life=False, max_episode_steps=None, normalize_returns=False):
     """Trains an Atari model with A2C (RMSProp, conv3 64) or ACKTR (K-FAC, conv3 32).
 
     ``num_envs`` is per GPU; with WORLD_SIZE > 1 (torchrun) every rank steps its own shard.
@@ -43,6 +44,10 @@ def train_a2c_acktr(acktr, env_id, num_envs, num_steps, checkpoint_path, model_n
     games only: a lost life is a terminal for the learner, and a step cap of N (1..2000) whose terminals
     are truncations -- the targets keep their bootstrap there (``model.truncations_placeholder``).
     Evaluation envs are built without episodic life (envs.games.evaluate counts terminals as games).
+    ``normalize_returns`` (``--normalize-returns``): rewards scaled by the running std of the discounted
+    return, per game (actorcritic.return_norm; groups from ReturnNormalizer.for_envs); its statistics
+    travel with the checkpoints.  A ReturnNormalizer of the caller's own is taken as it is (the caller
+    keeps it: scripts/learn_games.py logs its scale).
     ``checkpoint_path`` None: nothing is loaded or saved.  ``on_update(updates, model)`` is called
     after every update (learning curves: scripts/learn_games.py).
     """
@@ -62,7 +67,9 @@ def train_a2c_acktr(acktr, env_id, num_envs, num_steps, checkpoint_path, model_n
     conv3_num_filters = 32 if acktr else 64
     model = AtariModel(multi_env.observation_space, multi_env.action_space, conv3_num_filters, random_seed=seed)
     agent = MultiEnvAgent(multi_env, model, num_steps, mask_actions=mask_actions)
-    objective = A2CObjective(model, discount_factor=0.99, entropy_regularization_strength=0.01)
+    normalizer = make_normalizer(normalize_returns, multi_env)
+    objective = A2CObjective(model, discount_factor=0.99, entropy_regularization_strength=0.01,
+                             normalize_returns=normalizer)
 
     global_step = get_or_create_global_step()
     # 1e7 env-steps (4e7 frames) over the whole job; global steps = env-steps / batch
@@ -80,7 +87,7 @@ def train_a2c_acktr(acktr, env_id, num_envs, num_steps, checkpoint_path, model_n
 
     with Session() as session:
         if checkpoint_path is not None:
-            load_model(checkpoint_path, model, optimizer, global_step)
+            load_model(checkpoint_path, model, optimizer, global_step, objective)
         step = global_step.value
         updates = 0
         try:
@@ -113,16 +120,24 @@ def train_a2c_acktr(acktr, env_id, num_envs, num_steps, checkpoint_path, model_n
                 if on_update is not None:
                     on_update(updates, model)
                 if checkpoint_path is not None and step % 100 == 0 and step > 0 and parallel.rank() == 0:
-                    save_model(checkpoint_path, model_name, step, model, optimizer)
+                    save_model(checkpoint_path, model_name, step, model, optimizer, objective)
         except KeyboardInterrupt:
             print('Stop requested')
             if checkpoint_path is not None and parallel.rank() == 0:
-                save_model(checkpoint_path, model_name, step, model, optimizer)
+                save_model(checkpoint_path, model_name, step, model, optimizer, objective)
         finally:
             multi_env.close()
             if summary_writer is not None:
                 summary_writer.close()
     return model, optimizer
+
+
+def make_normalizer(normalize_returns, multi_env):
+    """``normalize_returns`` of the train functions -> None (falsy), the caller's ReturnNormalizer, or
+    (True) one with the groups of the envs."""
+    if isinstance(normalize_returns, ReturnNormalizer):
+        return normalize_returns
+    return ReturnNormalizer.for_envs(multi_env) if normalize_returns else None
 
 
 def create_environments(env_id, num_envs, seed=0, full_action_set=False):
@@ -190,18 +205,18 @@ def create_optimizer(acktr, model, learning_rate):
     return ClipGlobalNormOptimizer(optimizer, clip_norm=0.5)
 
 
-def load_model(checkpoint_path, model, optimizer, global_step):
+def load_model(checkpoint_path, model, optimizer, global_step, objective=None):
     path = checkpoint.latest(checkpoint_path)
     if path is None:
         print('No model loaded')
         return False
-    checkpoint.load(path, model, optimizer, global_step)
+    checkpoint.load(path, model, optimizer, global_step, objective=objective)
     print('Loaded model')
     return True
 
 
-def save_model(checkpoint_path, model_name, step, model, optimizer):
-    checkpoint.save(os.path.join(checkpoint_path, model_name), step, model, optimizer)
+def save_model(checkpoint_path, model_name, step, model, optimizer, objective=None):
+    checkpoint.save(os.path.join(checkpoint_path, model_name), step, model, optimizer, objective=objective)
     print('Saved model (step {})'.format(step))
 
 
@@ -220,4 +235,5 @@ if __name__ == '__main__':
     train_a2c_acktr(acktr, env_id, num_envs, num_steps, checkpoint_path, 'Atari-' + env_id, summary_path,
                     mask_actions='--mask-actions' in argv, game=game, episodic_life='--episodic-life' in argv,
                     max_episode_steps=(int(argv[argv.index('--max-episode-steps') + 1])
-                                       if '--max-episode-steps' in argv else None))
+                                       if '--max-episode-steps' in argv else None),
+                    normalize_returns='--normalize-returns' in argv)

@@ -21,7 +21,8 @@ from actorcritic.agents import MultiEnvAgent
 from actorcritic.envs.atari.model import AtariModel
 from actorcritic.examples.atari.a2c_acktr import (create_environments, create_game_environments,
                                                   episode_rewards_by_game,
-                                                   create_host_environments, load_model, save_model)
+                                                   create_host_environments, load_model, make_normalizer,
+                                                   save_model)
 from actorcritic.multi_env import MultiEnv
 from actorcritic.nn import AdamOptimizer, ClipGlobalNormOptimizer, linear_decay
 from actorcritic.objectives import PPOObjective
@@ -31,7 +32,7 @@ from actorcritic.session import Session, get_or_create_global_step, no_op
 def train_ppo(env_id, num_envs, num_steps, checkpoint_path, model_name, summary_path=None, max_updates=None, seed=0,
               log_every=10, num_epochs=4, num_minibatches=4, clip_range=0.1, value_clip_range=None,
               minibatch='envs', env_fns=None, mask_actions=False, game=None, on_update=None, episodic_life=False,
-              max_episode_steps=None):
+              max_episode_steps=None, normalize_returns=False):
     """Trains an Atari model (conv3 64) with PPO.
 
     ``num_envs`` is per GPU; with WORLD_SIZE > 1 (torchrun) every rank steps its own shard.
@@ -45,7 +46,7 @@ def train_ppo(env_id, num_envs, num_steps, checkpoint_path, model_name, summary_
     ``mask_actions`` (``--mask-actions``): invalid-action masking, as in a2c_acktr.train_a2c_acktr.
     ``game`` (``--game catch|breakout``, or a mixed batch: ``catch+breakout``), ``episodic_life``
     (``--episodic-life``), ``max_episode_steps`` (``--max-episode-steps N``), ``checkpoint_path`` None and
-    ``on_update``: as in a2c_acktr.train_a2c_acktr.
+    ``on_update`` and ``normalize_returns`` (``--normalize-returns``): as in a2c_acktr.train_a2c_acktr.
     """
     parallel.init_from_env()
     if game is None and (episodic_life or max_episode_steps is not None):
@@ -62,9 +63,10 @@ def train_ppo(env_id, num_envs, num_steps, checkpoint_path, model_name, summary_
 
     model = AtariModel(multi_env.observation_space, multi_env.action_space, 64, random_seed=seed)
     agent = MultiEnvAgent(multi_env, model, num_steps, mask_actions=mask_actions)
+    normalizer = make_normalizer(normalize_returns, multi_env)
     objective = PPOObjective(model, discount_factor=0.99, entropy_regularization_strength=0.01,
                              clip_range=clip_range, value_clip_range=value_clip_range, gae_lambda=0.95,
-                             normalize_advantages=True)
+                             normalize_advantages=True, normalize_returns=normalizer)
 
     global_step = get_or_create_global_step()
     # 1e7 env-steps (4e7 frames) over the whole job; global steps = env-steps / batch
@@ -81,7 +83,7 @@ def train_ppo(env_id, num_envs, num_steps, checkpoint_path, model_name, summary_
 
     with Session() as session:
         if checkpoint_path is not None:
-            load_model(checkpoint_path, model, optimizer, global_step)
+            load_model(checkpoint_path, model, optimizer, global_step, objective)
         step = global_step.value
         updates = 0
         try:
@@ -116,11 +118,11 @@ def train_ppo(env_id, num_envs, num_steps, checkpoint_path, model_name, summary_
                 if on_update is not None:
                     on_update(updates, model)
                 if checkpoint_path is not None and step % 100 == 0 and step > 0 and parallel.rank() == 0:
-                    save_model(checkpoint_path, model_name, step, model, optimizer)
+                    save_model(checkpoint_path, model_name, step, model, optimizer, objective)
         except KeyboardInterrupt:
             print('Stop requested')
             if checkpoint_path is not None and parallel.rank() == 0:
-                save_model(checkpoint_path, model_name, step, model, optimizer)
+                save_model(checkpoint_path, model_name, step, model, optimizer, objective)
         finally:
             multi_env.close()
             if summary_writer is not None:
@@ -148,4 +150,5 @@ if __name__ == '__main__':
     train_ppo(env_id, num_envs, num_steps, checkpoint_path, 'Atari-' + env_id, summary_path,
               mask_actions='--mask-actions' in argv, game=game, episodic_life='--episodic-life' in argv,
               max_episode_steps=(int(argv[argv.index('--max-episode-steps') + 1])
-                                 if '--max-episode-steps' in argv else None))
+                                 if '--max-episode-steps' in argv else None),
+              normalize_returns='--normalize-returns' in argv)

@@ -23,6 +23,15 @@ the value of the next observation -- row t+1 of the batch, or the bootstrap row 
 t = T-1 -- through the truncating forms of acmi_returns / acmi_gae (_ops.targets).
 Unfed, every terminal cuts it.
 
+Reward scaling (beyond the reference as well, off by default): ``normalize_returns`` takes a
+:class:`actorcritic.return_norm.ReturnNormalizer`; the targets are then formed from the
+rewards scaled by the running std of the discounted return of each env's group (game) --
+acmi_retnorm_scan, the moments summed over ranks, acmi_retnorm_apply -- written to a buffer
+of the update state; the fed tensor is not written.  The statistics advance once per
+``session.run`` that evaluates the targets (PPO's epochs and minibatches reuse them) -- also
+in a run that fetches only ``target_values``, unless the normalizer is ``frozen``.
+``normalized_rewards`` and ``return_stats`` are fetchable.
+
 :class:`PPOObjective` (also beyond the reference) shares those targets and
 advantages and replaces the loss by PPO's clipped surrogate (acmi_ppo_loss); its
 ``optimize_shared`` op takes several epochs of minibatch gradient steps per
@@ -115,6 +124,9 @@ class _Targets(Node):
         trunc = ctx.feeds.get(model.truncations_placeholder)
         if trunc is not None:  # time limits: those terminals keep their bootstrap (module docstring)
             trunc = _device_bool_u8(trunc, eng.device).reshape(N, T)
+        if obj._retnorm is not None:  # per-game reward scaling: once per run (this node is memoised)
+            rewards = obj._retnorm.normalize(rewards, terminals, obj._gamma, st.reward_buffer(N, T), eng.stream(),
+                                             eng.world_size)
         tables = obj._tables(T, eng.device) if obj._gae_lambda is None else None
         _ops.targets(rewards, terminals, fwd.flat_value, boot.flat_value, N, T, obj._gamma, obj._gae_lambda, tables,
                      st.targets, st.adv, eng.stream(), truncated=trunc)
@@ -122,6 +134,28 @@ class _Targets(Node):
             _normalize_advantages(eng, st.adv, N * T, obj._adv_eps)
         st.fwd = fwd
         return st
+
+
+class _ReturnStats(Node):
+    """The normalizer's stats ([G][3] f64: count, mean, M2) after this run's targets."""
+    name = 'return_stats'
+
+    def __init__(self, objective):
+        self.objective = objective
+
+    def _eval(self, ctx):
+        obj = self.objective
+        if obj._retnorm is None:
+            raise ValueError('return_stats needs an objective built with normalize_returns=')
+        ctx.eval(obj._targets_node)
+        return obj._retnorm.stats.clone()
+
+
+def _check_normalizer(normalize_returns):
+    from actorcritic.return_norm import ReturnNormalizer
+    if normalize_returns is not None and not isinstance(normalize_returns, ReturnNormalizer):
+        raise TypeError('normalize_returns takes a ReturnNormalizer or None, got {!r}'.format(normalize_returns))
+    return normalize_returns
 
 
 def _normalize_advantages(eng, adv, M, eps):
@@ -195,16 +229,18 @@ class A2CObjective(ActorCriticObjective):
     """A2C/ACKTR objective (objectives.py:82-175)."""
 
     def __init__(self, model, discount_factor=0.99, entropy_regularization_strength=0.01, name=None,
-                 gae_lambda=None, normalize_advantages=False, advantage_epsilon=1e-8):
+                 gae_lambda=None, normalize_advantages=False, advantage_epsilon=1e-8, normalize_returns=None):
         """The reference's arguments (objectives.py:100); ``gae_lambda`` (None: the
-        reference's n-step targets; a float in [0, 1]: GAE(lambda)) and
-        ``normalize_advantages`` are extensions beyond it (module docstring)."""
+        reference's n-step targets; a float in [0, 1]: GAE(lambda)), ``normalize_advantages``
+        and ``normalize_returns`` (a :class:`actorcritic.return_norm.ReturnNormalizer`) are
+        extensions beyond it (module docstring)."""
         if gae_lambda is not None and not 0.0 <= float(gae_lambda) <= 1.0:
             raise ValueError('gae_lambda must be in [0, 1] or None, got {}'.format(gae_lambda))
         self._model = model
         self._gamma = float(discount_factor)
         self._gae_lambda = None if gae_lambda is None else float(gae_lambda)
         self._normalize = bool(normalize_advantages)
+        self._retnorm = _check_normalizer(normalize_returns)
         self._adv_eps = float(advantage_epsilon)
         self._beta = float(entropy_regularization_strength)
         self._vcoef = 0.5
@@ -233,6 +269,23 @@ class A2CObjective(ActorCriticObjective):
     @property
     def advantage(self):
         return _TargetView(self._targets_node, 'adv')
+
+    @property
+    def normalized_rewards(self):
+        """The scaled rewards [env, step] the targets were formed from (``normalize_returns``)."""
+        if self._retnorm is None:
+            raise ValueError('normalized_rewards needs an objective built with normalize_returns=')
+        return _TargetView(self._targets_node, 'norm_rewards')
+
+    @property
+    def return_stats(self):
+        """The normalizer's per-group (count, mean, M2), [G][3] float64, after this run."""
+        return _ReturnStats(self)
+
+    @property
+    def return_normalizer(self):
+        """The ReturnNormalizer given as ``normalize_returns``, or None."""
+        return self._retnorm
 
     @property
     def policy_loss(self):
@@ -412,7 +465,7 @@ class PPOObjective(ActorCriticObjective):
 
     def __init__(self, model, discount_factor=0.99, entropy_regularization_strength=0.01, clip_range=0.1,
                  value_clip_range=None, gae_lambda=0.95, normalize_advantages=True, advantage_epsilon=1e-8,
-                 name=None):
+                 name=None, normalize_returns=None):
         if not float(clip_range) > 0.0:
             raise ValueError('clip_range must be positive, got {}'.format(clip_range))
         if value_clip_range is not None and not float(value_clip_range) > 0.0:
@@ -428,6 +481,7 @@ class PPOObjective(ActorCriticObjective):
         # 'minibatch': every gradient step normalises its own rows (PPOOptimizeOp), the batch is left alone
         self._normalize_minibatch = normalize_advantages == 'minibatch'
         self._normalize = not self._normalize_minibatch and bool(normalize_advantages)
+        self._retnorm = _check_normalizer(normalize_returns)
         self._adv_eps = float(advantage_epsilon)
         self._beta = float(entropy_regularization_strength)
         self._clip = float(clip_range)
@@ -498,6 +552,10 @@ class PPOObjective(ActorCriticObjective):
     @property
     def advantage(self):
         return _TargetView(self._targets_node, 'adv')
+
+    normalized_rewards = A2CObjective.normalized_rewards
+    return_stats = A2CObjective.return_stats
+    return_normalizer = A2CObjective.return_normalizer
 
     @property
     def policy_loss(self):

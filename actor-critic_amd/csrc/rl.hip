@@ -182,6 +182,102 @@ __global__ void adv_normalize_kernel(float* a, long long M, const double* mom, d
 }
 
 // ---------------------------------------------------------------------------
+// per-group reward scaling by the running std of the discounted return (an
+// option beyond the reference; baselines' VecNormalize(ret=True), one set of
+// statistics per game).  acmi.h states the maths.  Three launches an update:
+//   retnorm_scan_kernel    one thread per env: forward scan of R = gamma R + r
+//                          (float32, no contraction) from carry[n], the env's
+//                          (sum u, sum u^2) in double into ws[n][2]
+//   retnorm_groups_kernel  one wave per group: lane-strided over the envs in
+//                          ascending order, then the butterfly -- fixed order,
+//                          no atomics on the sums
+//   retnorm_apply_kernel   ONE block: thread g merges group g's (summed over
+//                          ranks) moments into stats[g] (Chan), a barrier, then
+//                          every thread scales.  One block because stats is
+//                          updated in place and every scale must see the merged
+//                          value: a second block could not tell which it read.
+//                          The batch is N*T floats (10240 at 512 x 20).
+// An env whose group id is >= G is counted in bad_envs, joins no group, keeps
+// its rewards as they are; its carry advances all the same.
+// ---------------------------------------------------------------------------
+constexpr int RETNORM_MAX_GROUPS = 64;
+constexpr int RETNORM_SCAN_BLOCK = 256;
+constexpr int RETNORM_APPLY_BLOCK = 1024;
+
+__global__ void retnorm_scan_kernel(const float* r, const uint8_t* d, const uint8_t* groups, int N, int T, int G,
+                                    float gamma, float* carry, double* part, int32_t* bad_envs) {
+  const int n = blockIdx.x * blockDim.x + threadIdx.x;
+  if (n >= N) return;
+  float R = carry[n];
+  double s = 0.0, q = 0.0;
+  for (int t = 0; t < T; ++t) {
+    const long long i = (long long)n * T + t;
+    R = __fadd_rn(__fmul_rn(R, gamma), r[i]);
+    const double u = R;
+    s += u;
+    q += u * u;  // (u*u is exact in double: a fused multiply-add rounds the same sum)
+    if (d[i] != 0) R = 0.f;
+  }
+  carry[n] = R;
+  part[2LL * n] = s;
+  part[2LL * n + 1] = q;
+  if (groups[n] >= G && bad_envs != nullptr) atomicAdd(bad_envs, 1);
+}
+
+__global__ void retnorm_groups_kernel(const double* part, const uint8_t* groups, int N, int T, double* moments) {
+  const int g = blockIdx.x;  // one wave per group
+  double c = 0.0, s = 0.0, q = 0.0;
+  for (int n = threadIdx.x; n < N; n += 64) {
+    if (groups[n] == g) c += 1.0, s += part[2LL * n], q += part[2LL * n + 1];
+  }
+  c = wave_sum_d(c);  // (a count of envs: exact)
+  s = wave_sum_d(s);
+  q = wave_sum_d(q);
+  if (threadIdx.x == 0) moments[3 * g] = c * (double)T, moments[3 * g + 1] = s, moments[3 * g + 2] = q;
+}
+
+__global__ void __launch_bounds__(RETNORM_APPLY_BLOCK)
+    retnorm_apply_kernel(const float* r, const uint8_t* groups, int N, int T, int G, const double* moments,
+                         double* stats, double eps, float clip, float* out, float* inv_out) {
+  __shared__ float inv[RETNORM_MAX_GROUPS];
+  const int g = threadIdx.x;
+  if (g < G) {
+    double n = stats[3 * g], mean = stats[3 * g + 1], M2 = stats[3 * g + 2];
+    const double c = moments[3 * g], s = moments[3 * g + 1], q = moments[3 * g + 2];
+    if (c > 0.0) {
+      const double mb = s / c;
+      const double M2b = fmax(q - s * s / c, 0.0);
+      const double tot = n + c;
+      const double dl = mb - mean;
+      mean += dl * c / tot;
+      M2 += M2b + dl * dl * n * c / tot;
+      n = tot;
+      stats[3 * g] = n, stats[3 * g + 1] = mean, stats[3 * g + 2] = M2;
+    }
+    const float v = n > 0.0 ? (float)(1.0 / sqrt(M2 / n + eps)) : 1.0f;
+    inv[g] = v;
+    if (inv_out != nullptr) inv_out[g] = v;
+  }
+  __syncthreads();
+  const long long M = (long long)N * T;
+  // elementwise (out may be r); element i = e*T + t, with (e, t) stepped along with i: no divide a turn
+  const int de = RETNORM_APPLY_BLOCK / T, dt = RETNORM_APPLY_BLOCK % T;
+  int e = (int)threadIdx.x / T, t = (int)threadIdx.x % T;
+  for (long long i = threadIdx.x; i < M; i += RETNORM_APPLY_BLOCK) {
+    const int ge = groups[e];
+    const float x = r[i];
+    float v = x;
+    if (ge < G) {
+      v = __fmul_rn(x, inv[ge]);
+      if (clip > 0.f) v = v > clip ? clip : (v < -clip ? -clip : v);  // (a NaN stays a NaN)
+    }
+    out[i] = v;
+    e += de, t += dt;
+    if (t >= T) t -= T, ++e;
+  }
+}
+
+// ---------------------------------------------------------------------------
 // A2C and PPO losses + head gradients: one thread per row, the row's policy
 // arithmetic and the block's sums stated once for both
 // ---------------------------------------------------------------------------
@@ -711,6 +807,39 @@ int acmi_adv_normalize(float* adv, int64_t M, const double* moments, double coun
   hipLaunchKernelGGL(adv_normalize_kernel, dim3(std::min<long long>(cdiv(M, 256), 1024)), dim3(256), 0,
                      (hipStream_t)stream, adv, (long long)M, moments, count, eps);
   ACMI_LAUNCH_CHECK("acmi_adv_normalize");
+  return ACMI_OK;
+}
+
+int64_t acmi_retnorm_ws_doubles(int64_t N) { return N < 1 ? 0 : 2 * N; }
+
+int acmi_retnorm_scan(const float* rewards, const uint8_t* terminals, const uint8_t* groups, int N, int T, int G,
+                      float gamma, float* carry, double* ws, double* moments, int32_t* bad_envs,
+                      acmi_stream_t stream) {
+  ACMI_REQUIRE(rewards && terminals && groups && carry && ws && moments, ACMI_ERR_ARG,
+               "acmi_retnorm_scan: a required pointer is NULL");
+  ACMI_REQUIRE(N >= 1 && T >= 1 && G >= 1 && G <= RETNORM_MAX_GROUPS, ACMI_ERR_ARG,
+               "acmi_retnorm_scan: N=%d, T=%d must be at least 1 and G=%d in 1..%d", N, T, G, RETNORM_MAX_GROUPS);
+  ACMI_REQUIRE(gamma >= 0.f && gamma <= 1.f, ACMI_ERR_ARG, "acmi_retnorm_scan: gamma=%g outside [0, 1]",
+               (double)gamma);
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(retnorm_scan_kernel, dim3(cdiv(N, RETNORM_SCAN_BLOCK)), dim3(RETNORM_SCAN_BLOCK), 0, s, rewards,
+                     terminals, groups, N, T, G, gamma, carry, ws, bad_envs);
+  hipLaunchKernelGGL(retnorm_groups_kernel, dim3(G), dim3(64), 0, s, ws, groups, N, T, moments);
+  ACMI_LAUNCH_CHECK("acmi_retnorm_scan");
+  return ACMI_OK;
+}
+
+int acmi_retnorm_apply(const float* rewards, const uint8_t* groups, int N, int T, int G, const double* moments,
+                       double* stats, double eps, float clip, float* out, float* inv_out, acmi_stream_t stream) {
+  ACMI_REQUIRE(rewards && groups && moments && stats && out, ACMI_ERR_ARG,
+               "acmi_retnorm_apply: a required pointer is NULL");
+  ACMI_REQUIRE(N >= 1 && T >= 1 && G >= 1 && G <= RETNORM_MAX_GROUPS, ACMI_ERR_ARG,
+               "acmi_retnorm_apply: N=%d, T=%d must be at least 1 and G=%d in 1..%d", N, T, G, RETNORM_MAX_GROUPS);
+  ACMI_REQUIRE(eps >= 0.0 && clip == clip, ACMI_ERR_ARG, "acmi_retnorm_apply: eps=%g must not be negative, clip=%g",
+               eps, (double)clip);
+  hipLaunchKernelGGL(retnorm_apply_kernel, dim3(1), dim3(RETNORM_APPLY_BLOCK), 0, (hipStream_t)stream, rewards,
+                     groups, N, T, G, moments, stats, eps, clip, out, inv_out);
+  ACMI_LAUNCH_CHECK("acmi_retnorm_apply");
   return ACMI_OK;
 }
 

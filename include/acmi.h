@@ -299,6 +299,44 @@ int acmi_adv_moments(const float* adv, int64_t M, double* ws, double* moments,
 int acmi_adv_normalize(float* adv, int64_t M, const double* moments, double count,
                        double eps, acmi_stream_t stream);
 
+/* Reward scaling by the running standard deviation of the discounted return,
+ * one set of statistics per group of envs (per game); an option beyond the
+ * reference (baselines' VecNormalize(ret=True)).  State across updates:
+ * carry[N] f32 (each env's running return, starts 0), stats[G][3] f64 (count,
+ * mean, M2 per group, starts 0), groups[N] u8; G in 1..64.  Per update, over
+ * rewards[N][T] f32 and terminals[N][T] u8 (a truncation is a terminal here):
+ *   scan    per env, ascending t, float32, no contraction: R = R*gamma,
+ *           R = R + r[n][t]; that R is the sample u[n][t]; a terminal sets
+ *           R = 0 after the sample; carry[n] = R at the end.
+ *   moments[g] = (c, s, q): the number of samples of group g's envs (N_g*T),
+ *           sum u and sum u^2, each u converted to double and summed in
+ *           double in a fixed order (no floating-point atomics: same bytes in,
+ *           same bytes out).  ws: acmi_retnorm_ws_doubles(N) doubles.
+ * A data-parallel caller sums the moments over ranks between the two calls.
+ *   merge   (acmi_retnorm_apply, once, one thread per group, double) for c > 0:
+ *           mb = s/c, M2b = max(q - s*s/c, 0), tot = n + c, d = mb - mean,
+ *           mean += d*c/tot, M2 += M2b + d*d*n*c/tot, n = tot (Chan et al.);
+ *           c == 0 leaves the group's stats alone (all-zero moments: frozen).
+ *   scale   inv[g] = f32(1/sqrt(M2/n + eps)) from the merged stats (n == 0:
+ *           1.0f); out = clamp(r*inv[groups[n]], -clip, +clip) in float32,
+ *           clip <= 0: no clamp.  out == rewards is allowed; inv_out ([G] f32)
+ *           is nullable.
+ * An env whose group id is >= G touches no memory outside the buffers, joins no
+ * group and keeps its rewards as they are (unscaled, unclamped); its carry
+ * advances all the same, and acmi_retnorm_scan counts it once per call in
+ * *bad_envs (device int32, nullable, accumulated).
+ * Three launches in all (scan 2, apply 1, the latter one workgroup), no host
+ * synchronisation.  ACMI_ERR_ARG before anything is enqueued: a null required
+ * pointer, N < 1, T < 1, G outside 1..64, gamma outside [0, 1], eps < 0. */
+int64_t acmi_retnorm_ws_doubles(int64_t N);
+int acmi_retnorm_scan(const float* rewards, const uint8_t* terminals,
+                      const uint8_t* groups, int N, int T, int G, float gamma,
+                      float* carry, double* ws, double* moments, int32_t* bad_envs,
+                      acmi_stream_t stream);
+int acmi_retnorm_apply(const float* rewards, const uint8_t* groups, int N, int T, int G,
+                       const double* moments, double* stats, double eps, float clip,
+                       float* out, float* inv_out, acmi_stream_t stream);
+
 /* ------------------------------------------------------------------------
  * A2C losses and their gradient w.r.t. the head outputs.  Replaces
  * objectives.py:132-154 and the head part of tf.gradients of

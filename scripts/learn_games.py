@@ -17,6 +17,9 @@ returns stay whole-game returns and compare across the settings.
 one line per game and point, with "eval_game".  --mask-actions: the 18-action head with every
 env's own set as its legal-action mask (for the evaluation the model's mask words are
 overwritten in place with the evaluation batch's and put back, so --eval-envs must be --envs).
+
+--normalize-returns trains with the rewards scaled by the running std of the discounted return,
+per game (actorcritic.return_norm); every line of a point then holds "inv", the scale per game.
 """
 import argparse
 import json
@@ -40,7 +43,7 @@ def run(args, seed, emit):
     N, T, E = args.envs, args.steps, args.episodes
     head = dict(algo=args.algo, game=args.game, seed=seed, envs=N, steps=T, eval_envs=args.eval_envs, eval_episodes=E,
                 episodic_life=args.episodic_life, max_episode_steps=args.max_episode_steps,
-                mask_actions=args.mask_actions)
+                mask_actions=args.mask_actions, normalize_returns=args.normalize_returns)
     eval_games = [g for g in GAMES if g in args.game.split('+')]
     mixed = len(eval_games) > 1
     # the head of the trained model: the mixed batch's (4) or the full set under masks (18)
@@ -58,6 +61,11 @@ def run(args, seed, emit):
     for g in eval_games:
         emit(dict(head, policy='uniform', updates=0, env_steps=0, **tag(g),
                   **stats(evaluate(None, eval_envs(g), episodes(g), uniform=True, seed=seed))))
+    norm = False
+    if args.normalize_returns:  # built here and handed to the example, so that its scale can be logged
+        from actorcritic.envs.games.host import env_game_ids
+        from actorcritic.return_norm import ReturnNormalizer
+        norm = ReturnNormalizer(env_game_ids(args.game, N), num_groups=len(GAMES), group_names=GAMES)
     t0 = time.perf_counter()
 
     def play(model, g):
@@ -76,16 +84,20 @@ def run(args, seed, emit):
         if updates % args.every == 0 or updates == args.updates:
             torch.cuda.synchronize()
             train_s = time.perf_counter() - t0
+            inv = {} if not norm else dict(inv={n: round(float(v), 4) for n, v in
+                                                    zip(norm.group_names, norm.inv.cpu().tolist())})
             for g in eval_games:
                 emit(dict(head, policy='sampled' if args.sample else 'greedy', updates=updates,
-                          env_steps=updates * N * T, wall_s=round(train_s, 2), **tag(g), **stats(play(model, g))))
+                          env_steps=updates * N * T, wall_s=round(train_s, 2), **tag(g), **inv,
+                          **stats(play(model, g))))
 
     if args.algo == 'ppo':
         train_ppo(args.game, N, T, None, args.game, max_updates=args.updates, seed=seed, game=args.game,
-                  on_update=on_update, mask_actions=args.mask_actions, **rules)
+                  on_update=on_update, mask_actions=args.mask_actions, normalize_returns=norm, **rules)
     else:
         train_a2c_acktr(args.algo == 'acktr', args.game, N, T, None, args.game, max_updates=args.updates, seed=seed,
-                        game=args.game, on_update=on_update, mask_actions=args.mask_actions, **rules)
+                        game=args.game, on_update=on_update, mask_actions=args.mask_actions,
+                        normalize_returns=norm, **rules)
 
 
 def main():
@@ -105,6 +117,8 @@ def main():
     ap.add_argument('--sample', action='store_true', help='evaluate draws from the policy instead of its mode')
     ap.add_argument('--episodic-life', action='store_true', help='train with a lost life as a terminal')
     ap.add_argument('--max-episode-steps', type=int, default=None, help='step cap (truncation), 1..2000')
+    ap.add_argument('--normalize-returns', action='store_true',
+                    help='scale rewards by the running std of the discounted return, per game')
     ap.add_argument('--out', default=None, help='also append the JSON lines to this file')
     args = ap.parse_args()
     if args.mask_actions and args.eval_envs != args.envs:
