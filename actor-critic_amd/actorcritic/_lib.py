@@ -66,6 +66,12 @@ class RolloutIO(ctypes.Structure):
                 ('tower_done', c_int), ('next_acts', c_vp), ('next_act_stride', c_i64), ('obs_copy', c_vp)]
 
 
+class RolloutGameIO(ctypes.Structure):
+    # acmi_rollout_game_io_t (its size: acmi_rollout_game_io_bytes, checked in load())
+    _fields_ = [('io', RolloutIO), ('state', GameState), ('games', c_vp), ('rules', GameRules),
+                ('truncated', c_vp), ('bad_envs', c_vp), ('pend', c_vp)]
+
+
 # name -> (restype, argtypes)
 _SIGS = {
     'acmi_last_error': (ctypes.c_char_p, []),
@@ -183,6 +189,11 @@ _SIGS = {
     'acmi_game_step_mixed': (c_int, [ctypes.POINTER(GameState), c_vp, ctypes.POINTER(GameRules), c_int, c_int,
                                      c_u32, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp,
                                      c_vp]),
+    # the fused rollout step over the device games: legal is nullable (one entry point)
+    'acmi_game_pend_ints': (c_int, []),
+    'acmi_rollout_game_io_bytes': (c_i64, []),
+    'acmi_rollout_step_games': (c_int, [ctypes.POINTER(Net), c_vp, c_i64, c_int, ctypes.POINTER(Acts), c_i64,
+                                        ctypes.POINTER(RolloutGameIO), c_vp, c_vp]),
     'acmi_atari_preprocess': (c_int, [c_vp, c_i64, c_i64, c_vp, c_int, c_int, c_int, c_vp, c_i64, c_vp]),
     'acmi_atari_stack': (c_int, [c_vp, c_i64, c_i64, c_vp, c_int, c_int, c_int, c_vp, c_int, c_vp, c_vp,
                                  c_i64, c_vp]),
@@ -240,6 +251,9 @@ def load():
             fn.argtypes = args
         if lib.acmi_abi_version() != 4:
             raise ImportError('libacmi ABI mismatch')
+        if hasattr(lib, 'acmi_rollout_game_io_bytes') and \
+                int(lib.acmi_rollout_game_io_bytes()) != ctypes.sizeof(RolloutGameIO):
+            raise ImportError('libacmi acmi_rollout_game_io_t layout mismatch')
         _lib = lib
     return _lib
 

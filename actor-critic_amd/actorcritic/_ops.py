@@ -72,6 +72,13 @@ def rollout_step(net, obs, img_stride, B, acts, act_img_stride, io, stream, lega
           (_p(legal),), (stream,))
 
 
+def rollout_step_games(net, obs, img_stride, B, acts, act_img_stride, gio, stream, legal=None):
+    """acmi_rollout_step_games: net, acts, gio (_lib.RolloutGameIO) by reference; legal is
+    an argument of the one entry point (None: unmasked)."""
+    _lib.call('acmi_rollout_step_games', ctypes.byref(net), _p(obs), img_stride, B, ctypes.byref(acts),
+              act_img_stride, ctypes.byref(gio), _p(legal), stream)
+
+
 def output_stats(net, B, acts, bwd, seed, row_offset, counter, g_stats, ws, ws_floats, stream, legal=None):
     """net, acts, bwd: the ctypes structs (passed by reference)."""
     _call('acmi_kfac_output_stats', 'acmi_kfac_output_stats_masked',

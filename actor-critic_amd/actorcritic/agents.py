@@ -95,8 +95,8 @@ class _RolloutBuffers(object):
         self.use_graph = os.environ.get('ACMI_ROLLOUT_GRAPH', '0') == '1'
         # the fused step (acmi_rollout_step) takes up to 31 actions; wider action sets
         # step unfused: forward + sampler + env step, the ACMI_ROLLOUT_FUSED=0 path.
-        # So does an env that says ``fused_step = False`` (the fused tail holds the
-        # synthetic stepper: envs.games.DeviceGameEnvs); no such attribute = fused
+        # So does an env that says ``fused_step = False`` (envs.games.DeviceGameEnvs
+        # unless built with fused_step=True); no such attribute = fused
         self.fused = (os.environ.get('ACMI_ROLLOUT_FUSED', '1') != '0' and
                       engine.A <= _lib.ROLLOUT_STEP_MAX_ACTIONS and
                       bool(getattr(env, 'fused_step', True)))
@@ -384,11 +384,18 @@ def _half_step(eng, env, rb, h, N2, T, A, t, seed, dev_ctr=False, fuse=False):
         src_t, sstride = (rb.next_obs.data_ptr() + n0 * OBS_BYTES, OBS_BYTES) if t == 0 else (src, T * OBS_BYTES)
         # actions straight into the [N, T] batch (element b at [b*T], like the rewards)
         act_nt = rb.actions.data_ptr() + 4 * row
-        io = _lib.RolloutIO(seed, 0, ctr, ctr_dev, row0, act_nt, eng._bad_rows.data_ptr(), env.range_state(n0),
+        # an env with a fused step of its own (envs.games.DeviceGameEnvs) brings its
+        # entry point and the rest of its io: rollout_step; the others acmi_rollout_step
+        own = getattr(env, 'rollout_step', None)
+        io = _lib.RolloutIO(seed, 0, ctr, ctr_dev, row0, act_nt, eng._bad_rows.data_ptr(),
+                            _lib.EnvState() if own else env.range_state(n0),
                             env.env_offset + n0, env.seed, dst, dstride, rew, term, ep, T,
                             1 if fuse and t > 0 else 0, ctypes.addressof(nxt) if nxt is not None else None, T,
                             src if t == 0 else None)
-        _ops.rollout_step(eng.net(), src_t, sstride, N2, acts, T, io, eng.stream(), legal=legal)
+        if own:
+            own(eng.net(), src_t, sstride, n0, N2, acts, T, io, eng.stream(), legal=legal, **_trunc_arg(rb, row))
+        else:
+            _ops.rollout_step(eng.net(), src_t, sstride, N2, acts, T, io, eng.stream(), legal=legal)
         return
     eng.forward(src, N2, acts, want_value=True, img_stride=T * OBS_BYTES, act_stride=T)
     _ops.sample_actions(rb.acts.logits.data_ptr() + 4 * row * A, T * A, N2, A, seed, 0, ctr, row0, act_t,

@@ -17,7 +17,7 @@ import ctypes
 import numpy as np
 import torch
 
-from actorcritic import _lib, spaces
+from actorcritic import _lib, _ops, spaces
 from actorcritic._engine import OBS_BYTES
 from actorcritic.envs.atari.wrappers import EpisodeInfoBatch, _mask_tensor, action_mask_bits
 from actorcritic.envs.games.host import (GAME_ACTIONS, GAMES, STATE_INTS, HostGame, check_max_episode_steps,
@@ -63,14 +63,20 @@ class DeviceGameEnvs(object):
     holds every env's own set (4-action head: catch 0b0111, breakout 0b1111).  The rules
     apply to every env.  ``bad_envs`` (device int32 [1]) counts envs whose id the kernel
     refused; ids are validated here, so it stays 0.
+
+    ``fused_step=True`` (opt-in) puts the envs on the rollout's fused step
+    (``acmi_rollout_step_games``: heads, draw, game step and the next step's conv tower in
+    one kernel per env), bit-identical to the default three-call chain; ``step_into``,
+    ``step`` and :func:`evaluate` are unchanged.  The instance then owns the zeroed
+    pending buffer of the split form (``_pend``), which ``reset_into`` clears.
     """
 
-    # acmi_rollout_step's tail hard-wires the synthetic stepper: the rollout steps
-    # these envs unfused (forward + sampler + step_into), see agents._RolloutBuffers
+    # Off unless asked for (the keyword): the rollout steps these envs through forward +
+    # sampler + step_into, see agents._RolloutBuffers; True: through rollout_step below
     fused_step = False
 
     def __init__(self, game, num_envs, num_actions=None, seed=0, env_offset=0, device=None, episodic_life=False,
-                 max_episode_steps=None):
+                 max_episode_steps=None, fused_step=False):
         _lib.require_gpu()
         self.episodic_life = bool(episodic_life)
         self.max_episode_steps = check_max_episode_steps(max_episode_steps)
@@ -123,6 +129,12 @@ class DeviceGameEnvs(object):
             self._games_base, self._bad_ptr = self.games_tensor.data_ptr(), self.bad_envs.data_ptr()
         self._states = {}
         self.state = self.range_state(0)
+        if fused_step:
+            self.fused_step = True
+            # post-step states of the split form (B <= 64), committed by the next step's fc4
+            # launch; an entry is int32 x acmi_game_pend_ints(), a multiple of 16 bytes
+            self._pend_ints = int(lib.acmi_game_pend_ints())
+            self._pend = torch.zeros((N, self._pend_ints), dtype=torch.int32, device=self.device)
         self._obs = torch.zeros((N, 84, 84, 4), dtype=torch.uint8, device=self.device)
 
     def _stream(self):
@@ -143,6 +155,8 @@ class DeviceGameEnvs(object):
         return tuple(t.cpu().numpy() for t in (self._episode, self._step, self._total, self._done, self._vars))
 
     def reset_into(self, obs_ptr, stride=OBS_BYTES):
+        if self.fused_step:  # a stale entry must never be committed over the reset state
+            self._pend.zero_()
         if self.is_mixed:
             _lib.call('acmi_game_reset_mixed', ctypes.byref(self.state), self._games_base, self.num_envs,
                       self.env_offset, self.seed, ctypes.c_void_p(obs_ptr), stride, self._bad_ptr, self._stream())
@@ -183,6 +197,22 @@ class DeviceGameEnvs(object):
                   ctypes.c_void_p(actions_ptr), ctypes.c_void_p(obs_in_ptr), in_stride, ctypes.c_void_p(obs_out_ptr),
                   out_stride, ctypes.c_void_p(rew_ptr), ctypes.c_void_p(term_ptr), ctypes.c_void_p(ep_ptr), ld,
                   self._stream())
+
+    def rollout_step(self, net, obs, img_stride, n0, n, acts, act_img_stride, io, stream, legal=None,
+                     trunc_ptr=None):
+        """The fused rollout step of envs n0 .. n0+n-1 (``fused_step=True`` envs): ``io`` is
+        the _lib.RolloutIO the rollout built for them (its ``state`` is not read); the game
+        state, games and pending pointers go with n0, as in step_range_into."""
+        if not self.fused_step:
+            raise ValueError('these envs were built without fused_step=True')
+        if not (0 <= n0 and 0 <= n and n0 + n <= self.num_envs):
+            raise ValueError('envs {} .. {} outside the batch of {}'.format(n0, n0 + n - 1, self.num_envs))
+        if trunc_ptr is not None and not self.emits_truncations:
+            raise ValueError('these envs emit no truncations (episodic_life / max_episode_steps are off)')
+        gio = _lib.RolloutGameIO(io, self.range_state(n0), self._games_base + n0 if self.is_mixed else None,
+                                 self._rules, trunc_ptr, self._bad_ptr if self.is_mixed else None,
+                                 self._pend.data_ptr() + 4 * self._pend_ints * n0)
+        _ops.rollout_step_games(net, obs, img_stride, n, acts, act_img_stride, gio, stream, legal=legal)
 
     # -- gym-like batched API (as SyntheticAtariEnvs) ---------------------------
     def reset(self):

@@ -25,7 +25,8 @@ from actorcritic.session import Session, get_or_create_global_step, no_op
 
 def train_a2c_acktr(acktr, env_id, num_envs, num_steps, checkpoint_path, model_name, summary_path=None,
                     max_updates=None, seed=0, log_every=10, env_fns=None, mask_actions=False, game=None,
-                    on_update=None, episodic_life=False, max_episode_steps=None, normalize_returns=False):
+                    on_update=None, episodic_life=False, max_episode_steps=None, normalize_returns=False,
+                    fused_games=False):
     """Trains an Atari model with A2C (RMSProp, conv3 64) or ACKTR (K-FAC, conv3 32).
 
     ``num_envs`` is per GPU; with WORLD_SIZE > 1 (torchrun) every rank steps its own shard.
@@ -48,16 +49,18 @@ def train_a2c_acktr(acktr, env_id, num_envs, num_steps, checkpoint_path, model_n
     return, per game (actorcritic.return_norm; groups from ReturnNormalizer.for_envs); its statistics
     travel with the checkpoints.  A ReturnNormalizer of the caller's own is taken as it is (the caller
     keeps it: scripts/learn_games.py logs its scale).
+    ``fused_games`` (``--fused-games``), device games only: the rollout's fused step
+    (DeviceGameEnvs(fused_step=True)), bit-identical to the default three-call chain.
     ``checkpoint_path`` None: nothing is loaded or saved.  ``on_update(updates, model)`` is called
     after every update (learning curves: scripts/learn_games.py).
     """
     parallel.init_from_env()
-    if game is None and (episodic_life or max_episode_steps is not None):
-        raise ValueError('episodic_life and max_episode_steps need a device game (game=)')
+    if game is None and (episodic_life or max_episode_steps is not None or fused_games):
+        raise ValueError('episodic_life, max_episode_steps and fused_games need a device game (game=)')
     if game is not None:
         multi_env = MultiEnv(create_game_environments(game, num_envs, seed=seed, full_action_set=mask_actions,
                                                       episodic_life=episodic_life,
-                                                      max_episode_steps=max_episode_steps))
+                                                      max_episode_steps=max_episode_steps, fused_step=fused_games))
     elif env_fns is not None:
         multi_env = create_host_environments(env_fns)
         num_envs = multi_env.num_envs
@@ -152,17 +155,19 @@ def create_environments(env_id, num_envs, seed=0, full_action_set=False):
 
 
 def create_game_environments(game, num_envs, seed=0, full_action_set=False, episodic_life=False,
-                             max_episode_steps=None, env_offset=None):
+                             max_episode_steps=None, env_offset=None, fused_step=False):
     """This rank's shard of a device game ('catch', 'breakout') or of a mixed batch (a pattern such as
     'catch+breakout': the game follows the global env id, so the shards agree with one large batch).
     ``full_action_set``: under the 18-action head, every env's own actions in ``legal_action_masks``.
     ``episodic_life`` and ``max_episode_steps``: DeviceGameEnvs' (training envs only: evaluate()
-    refuses episodic life).  ``env_offset``: global id of the first env, default rank * num_envs."""
+    refuses episodic life).  ``env_offset``: global id of the first env, default rank * num_envs.
+    ``fused_step``: DeviceGameEnvs' (the rollout's fused step; off by default)."""
     from actorcritic.envs.games import DeviceGameEnvs
     if env_offset is None:
         env_offset = parallel.rank() * num_envs
     return DeviceGameEnvs(game, num_envs, num_actions=18 if full_action_set else None, seed=seed,
-                          env_offset=env_offset, episodic_life=episodic_life, max_episode_steps=max_episode_steps)
+                          env_offset=env_offset, episodic_life=episodic_life, max_episode_steps=max_episode_steps,
+                          fused_step=fused_step)
 
 
 def episode_rewards_by_game(batched, episode_rewards):
@@ -236,4 +241,4 @@ if __name__ == '__main__':
                     mask_actions='--mask-actions' in argv, game=game, episodic_life='--episodic-life' in argv,
                     max_episode_steps=(int(argv[argv.index('--max-episode-steps') + 1])
                                        if '--max-episode-steps' in argv else None),
-                    normalize_returns='--normalize-returns' in argv)
+                    normalize_returns='--normalize-returns' in argv, fused_games='--fused-games' in argv)

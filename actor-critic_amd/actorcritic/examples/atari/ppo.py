@@ -32,7 +32,7 @@ from actorcritic.session import Session, get_or_create_global_step, no_op
 def train_ppo(env_id, num_envs, num_steps, checkpoint_path, model_name, summary_path=None, max_updates=None, seed=0,
               log_every=10, num_epochs=4, num_minibatches=4, clip_range=0.1, value_clip_range=None,
               minibatch='envs', env_fns=None, mask_actions=False, game=None, on_update=None, episodic_life=False,
-              max_episode_steps=None, normalize_returns=False):
+              max_episode_steps=None, normalize_returns=False, fused_games=False):
     """Trains an Atari model (conv3 64) with PPO.
 
     ``num_envs`` is per GPU; with WORLD_SIZE > 1 (torchrun) every rank steps its own shard.
@@ -46,15 +46,16 @@ def train_ppo(env_id, num_envs, num_steps, checkpoint_path, model_name, summary_
     ``mask_actions`` (``--mask-actions``): invalid-action masking, as in a2c_acktr.train_a2c_acktr.
     ``game`` (``--game catch|breakout``, or a mixed batch: ``catch+breakout``), ``episodic_life``
     (``--episodic-life``), ``max_episode_steps`` (``--max-episode-steps N``), ``checkpoint_path`` None and
-    ``on_update`` and ``normalize_returns`` (``--normalize-returns``): as in a2c_acktr.train_a2c_acktr.
+    ``on_update``, ``normalize_returns`` (``--normalize-returns``) and ``fused_games`` (``--fused-games``): as in
+    a2c_acktr.train_a2c_acktr.
     """
     parallel.init_from_env()
-    if game is None and (episodic_life or max_episode_steps is not None):
-        raise ValueError('episodic_life and max_episode_steps need a device game (game=)')
+    if game is None and (episodic_life or max_episode_steps is not None or fused_games):
+        raise ValueError('episodic_life, max_episode_steps and fused_games need a device game (game=)')
     if game is not None:
         multi_env = MultiEnv(create_game_environments(game, num_envs, seed=seed, full_action_set=mask_actions,
                                                       episodic_life=episodic_life,
-                                                      max_episode_steps=max_episode_steps))
+                                                      max_episode_steps=max_episode_steps, fused_step=fused_games))
     elif env_fns is not None:
         multi_env = create_host_environments(env_fns)
         num_envs = multi_env.num_envs
@@ -151,4 +152,4 @@ if __name__ == '__main__':
               mask_actions='--mask-actions' in argv, game=game, episodic_life='--episodic-life' in argv,
               max_episode_steps=(int(argv[argv.index('--max-episode-steps') + 1])
                                  if '--max-episode-steps' in argv else None),
-              normalize_returns='--normalize-returns' in argv)
+              normalize_returns='--normalize-returns' in argv, fused_games='--fused-games' in argv)

@@ -60,14 +60,17 @@ struct Fc4Commit {
   PendState* pend;
   acmi_env_state_t st;
   int B;
+  __device__ __forceinline__ void run() const { env_commit_pending(st, pend, B); }
 };
 // CT: 32-column tiles per wave (2; 1 at small batches: twice the blocks, half
 // the MFMA chain per wave)
-template <int CT>
+// Commit: whose pending states (Fc4Commit: the synthetic stepper's; the device games
+// bring their own, forward.hpp GameFc4Commit) -- {pend, st, B} and run()
+template <int CT, class Commit = Fc4Commit>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1)))
 void fc4_roll_kernel(const float* a3, long long lda, int B, int K, const char* w4p, int nz, int chunk_steps,
-                     float* part, const unsigned* hdr, Fc4Commit cm) {
-  if (cm.B > 0 && blockIdx.x == 0) env_commit_pending(cm.st, cm.pend, cm.B);
+                     float* part, const unsigned* hdr, Commit cm) {
+  if (cm.B > 0 && blockIdx.x == 0) cm.run();
   constexpr int D = kFc4Depth, NSLOT = D + 1;
   constexpr int NG = 512 / (128 * CT);  // column groups of 4 waves
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -139,8 +142,9 @@ void fc4_roll_kernel(const float* a3, long long lda, int B, int K, const char* w
 inline bool fc4_roll_ok(const float* a3, long long lda, int K, int chunk) {
   return !(chunk % 16 || K % 16 || (lda % 4) || ((uintptr_t)a3 % 16));
 }
+template <class Commit = Fc4Commit>
 inline bool launch_fc4_roll(const float* a3, long long lda, int B, int K, const char* w4p, int nz, int chunk,
-                            float* part, const unsigned* hdr, hipStream_t s, Fc4Commit cm = Fc4Commit{}) {
+                            float* part, const unsigned* hdr, hipStream_t s, Commit cm = Commit{}) {
   if (!fc4_roll_ok(a3, lda, K, chunk)) return false;
   const int cs = chunk / 16;
 #ifndef ACMI_FC4_SMALL_CT  // column tiles per wave at batches <= 64
@@ -151,10 +155,10 @@ inline bool launch_fc4_roll(const float* a3, long long lda, int B, int K, const 
 #endif
   if (B <= ACMI_FC4_CT1_MAXB && ACMI_FC4_SMALL_CT == 1) {
     const dim3 grid(nz * ((B + 31) / 32) * 4), blk(256);
-    hipLaunchKernelGGL(fc4_roll_kernel<1>, grid, blk, 0, s, a3, lda, B, K, w4p, nz, cs, part, hdr, cm);
+    hipLaunchKernelGGL((fc4_roll_kernel<1, Commit>), grid, blk, 0, s, a3, lda, B, K, w4p, nz, cs, part, hdr, cm);
   } else {
     const dim3 grid(nz * ((B + 31) / 32) * 2), blk(256);
-    hipLaunchKernelGGL(fc4_roll_kernel<2>, grid, blk, 0, s, a3, lda, B, K, w4p, nz, cs, part, hdr, cm);
+    hipLaunchKernelGGL((fc4_roll_kernel<2, Commit>), grid, blk, 0, s, a3, lda, B, K, w4p, nz, cs, part, hdr, cm);
   }
   return true;
 }

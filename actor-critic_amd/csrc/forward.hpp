@@ -1,4 +1,4 @@
-// The forward (net.hip's acmi_forward / acmi_forward_strided / acmi_rollout_step):
+// The forward (net.hip's acmi_forward / acmi_forward_strided / acmi_rollout_step[_games]):
 // the per-layer epilogue and mask kernel, the heads kernel and the rollout tails
 // (alone, fused with the next step's tower, split over kSplitParts workgroups),
 // fc4's split plan with the table of split counts that have a compiled heads /
@@ -17,6 +17,7 @@
 #include "conv1u8.hpp"
 #include "convfwd3.hpp"
 #include "fc4roll.hpp"
+#include "games.hpp"
 #include "gemm.hpp"
 #include "gemm3.hpp"
 #include "stepper.hpp"
@@ -75,23 +76,117 @@ struct TailArgs {
   const uint32_t* legal = nullptr;
 };
 constexpr int kMaxHeads = 32;
+
+// The env a tail steps is a policy (rollout_tail_body's Env): its kernel arguments
+// (Args: io, obs, img_stride, legal as in TailArgs, plus its own), the pre-step state it
+// loads ahead of the heads (Pre, with the stack words in old[]), the whole-block step,
+// the split form's part step and its pending entry (Pend), and the host's half of the
+// pending contract (pend_area, commit).  SynthEnv is the synthetic stepper of
+// stepper.hpp (acmi_rollout_step); GameEnv the device games of games.hpp
+// (acmi_rollout_step_games).
+struct SynthEnv {
+  using Args = TailArgs;
+  using Pre = EnvPre;
+  using Pend = PendState;
+  using Commit = Fc4Commit;
+  static __device__ __forceinline__ void prefetch(const Args& ta, int row, Pre& pre) {
+    env_prefetch(ta.io.state, row, ta.obs + (long long)row * ta.img_stride, pre);
+  }
+  static __device__ __forceinline__ void step_block(const Args& ta, int row, uint32_t action, const Pre& pre,
+                                                    uint4* mirror) {
+    const acmi_rollout_io_t& io = ta.io;
+    env_step_block_pre(io.state, row, (uint32_t)(io.env_offset + row), io.env_seed, action, pre,
+                       io.obs_out + (long long)row * io.out_stride, io.rewards, io.terminals,
+                       io.episode_rewards, io.ld, mirror);
+  }
+  static __device__ __forceinline__ void step_part(const Args& ta, int row, uint32_t action, int spart,
+                                                   uint4* mirror, bool writer, Pend* pend) {
+    const acmi_rollout_io_t& io = ta.io;
+    env_step_part(io.state, row, (uint32_t)(io.env_offset + row), io.env_seed, action,
+                  ta.obs + (long long)row * ta.img_stride, split_word_lo(spart), split_word_hi(spart),
+                  split_own_lo(spart), split_own_hi(spart), io.obs_out + (long long)row * io.out_stride,
+                  io.obs_copy ? io.obs_copy + (long long)row * io.out_stride : nullptr, mirror, writer, io.rewards,
+                  io.terminals, io.episode_rewards, io.ld, pend);
+  }
+  // the pending states sit after fc4's slabs in the forward workspace
+  // (acmi_forward_ws_floats reserves them at B <= kSplitMaxB)
+  static Pend* pend_area(const Args&, const acmi_acts_t* a, int nz, int B) {
+    return a->ws_floats >= (long long)nz * (B + 1) * 512 + (long long)B * (sizeof(PendState) / 4)
+               ? reinterpret_cast<PendState*>(a->ws + (long long)nz * (B + 1) * 512)
+               : nullptr;
+  }
+  static Commit commit(const Args* ta, Pend* pend, int B) {
+    return Commit{pend, ta ? ta->io.state : acmi_env_state_t{}, pend ? B : 0};
+  }
+};
+
+// acmi_rollout_step_games: io.state is not read; the game is read per env from
+// game.games where that is given -- a run-time test of the pointer, one kernel per
+// form ("Fused step").  pend: the caller's pending area (host side only).
+struct GameTailArgs {
+  acmi_rollout_io_t io;
+  const uint8_t* obs;
+  long long img_stride;
+  const uint32_t* legal;
+  GameCall game;
+  uint8_t* truncated;
+  GamePend* pend;
+};
+struct GameFc4Commit {
+  GamePend* pend;
+  acmi_game_state_t st;
+  int B;
+  __device__ __forceinline__ void run() const { game_commit_pending(st, pend, B); }
+};
+struct GameEnv {
+  using Args = GameTailArgs;
+  using Pre = GamePre;
+  using Pend = GamePend;
+  using Commit = GameFc4Commit;
+  static __device__ __forceinline__ GameOut outs(const Args& ta) {
+    return GameOut{ta.io.rewards, ta.io.terminals, ta.truncated, ta.io.episode_rewards, ta.io.ld};
+  }
+  static __device__ __forceinline__ void prefetch(const Args& ta, int row, Pre& pre) {
+    game_prefetch<true>(ta.game, row, ta.obs + (long long)row * ta.img_stride, pre);
+  }
+  static __device__ __forceinline__ void step_block(const Args& ta, int row, uint32_t action, const Pre& pre,
+                                                    uint4* mirror) {
+    game_step_block_pre<true>(ta.game, row, (uint32_t)(ta.io.env_offset + row), action, pre,
+                              ta.io.obs_out + (long long)row * ta.io.out_stride, outs(ta), mirror);
+  }
+  static __device__ __forceinline__ void step_part(const Args& ta, int row, uint32_t action, int spart,
+                                                   uint4* mirror, bool writer, Pend* pend) {
+    const acmi_rollout_io_t& io = ta.io;
+    game_step_part(ta.game, row, (uint32_t)(io.env_offset + row), action, ta.obs + (long long)row * ta.img_stride,
+                   split_word_lo(spart), split_word_hi(spart), split_own_lo(spart), split_own_hi(spart),
+                   io.obs_out + (long long)row * io.out_stride,
+                   io.obs_copy ? io.obs_copy + (long long)row * io.out_stride : nullptr, mirror, writer, outs(ta),
+                   pend);
+  }
+  static Pend* pend_area(const Args& ta, const acmi_acts_t*, int, int) { return ta.pend; }
+  static Commit commit(const Args* ta, Pend* pend, int B) {
+    return Commit{pend, ta ? ta->game.st : acmi_game_state_t{}, pend ? B : 0};
+  }
+};
+static_assert(kGameWords == kEnvWords && kGameFrameWords == FRAME_WORDS && kGameThreads == kEnvThreads,
+              "the tails file the stacks of either env with one loop");
 // sx [512], sl [kMaxHeads], s_action: the block's scratch in LDS; mirror
 // (nullable): the new stack also goes there (the fused next-step tower's image)
 // SPLIT (towersplit.hpp): one of kSplitParts workgroups of env `row` (part `spart`):
 // the heads and the draw are computed by every part (the same arithmetic, so the
 // same action), only part 0 stores them; the env step builds the stack words the
 // part's tower needs (env_step_part) and the post-step state goes to pend.
-template <int NZ, bool SPLIT = false>
+template <int NZ, bool SPLIT = false, class Env = SynthEnv>
 __device__ __forceinline__ void rollout_tail_body(
     const float* part, int nz, const float* b4, float* a4, long long a4_stride, int B,
     const float* wpi, const float* bpi, const float* wv, const float* bv, int A, float* logits,
-    long long l_stride, float* value, long long v_stride, const TailArgs& ta, float* sx, float* sl,
-    int& s_action, uint4* mirror, int row = -1, int spart = 0, PendState* pend = nullptr) {
+    long long l_stride, float* value, long long v_stride, const typename Env::Args& ta, float* sx, float* sl,
+    int& s_action, uint4* mirror, int row = -1, int spart = 0, typename Env::Pend* pend = nullptr) {
   if (row < 0) row = blockIdx.x;
   const bool writer = spart == 0;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  EnvPre pre;  // the env's state and current stack: in flight during the heads
-  if constexpr (!SPLIT) env_prefetch(ta.io.state, row, ta.obs + (long long)row * ta.img_stride, pre);
+  typename Env::Pre pre;  // the env's state and current stack: in flight during the heads
+  if constexpr (!SPLIT) Env::prefetch(ta, row, pre);
   if (!SPLIT && ta.io.obs_copy) {  // the stacks this step read, filed where the batch keeps them
     uint4* cp = reinterpret_cast<uint4*>(ta.io.obs_copy + (long long)row * ta.io.out_stride);
 #pragma unroll
@@ -171,29 +266,20 @@ __device__ __forceinline__ void rollout_tail_body(
     s_action = y;
   }
   __syncthreads();
-  if constexpr (SPLIT) {
-    env_step_part(io.state, row, (uint32_t)(io.env_offset + row), io.env_seed, (uint32_t)s_action,
-                  ta.obs + (long long)row * ta.img_stride, split_word_lo(spart), split_word_hi(spart),
-                  split_own_lo(spart), split_own_hi(spart), io.obs_out + (long long)row * io.out_stride,
-                  io.obs_copy ? io.obs_copy + (long long)row * io.out_stride : nullptr, mirror, writer, io.rewards,
-                  io.terminals, io.episode_rewards, io.ld, pend);
-  } else {
-    env_step_block_pre(io.state, row, (uint32_t)(io.env_offset + row), io.env_seed, (uint32_t)s_action, pre,
-                       io.obs_out + (long long)row * io.out_stride, io.rewards, io.terminals,
-                       io.episode_rewards, io.ld, mirror);
-  }
+  if constexpr (SPLIT) Env::step_part(ta, row, (uint32_t)s_action, spart, mirror, writer, pend);
+  else Env::step_block(ta, row, (uint32_t)s_action, pre, mirror);
 }
 
-template <int NZ>
+template <int NZ, class Env = SynthEnv>
 __global__ __launch_bounds__(256) void rollout_tail_kernel(
     const float* part, int nz, const float* b4, float* a4, long long a4_stride, int B,
     const float* wpi, const float* bpi, const float* wv, const float* bv, int A, float* logits,
-    long long l_stride, float* value, long long v_stride, TailArgs ta) {
+    long long l_stride, float* value, long long v_stride, typename Env::Args ta) {
   __shared__ float sx[512];
   __shared__ float sl[kMaxHeads];
   __shared__ int s_action;
-  rollout_tail_body<NZ>(part, nz, b4, a4, a4_stride, B, wpi, bpi, wv, bv, A, logits, l_stride, value, v_stride,
-                        ta, sx, sl, s_action, nullptr);
+  rollout_tail_body<NZ, false, Env>(part, nz, b4, a4, a4_stride, B, wpi, bpi, wv, bv, A, logits, l_stride, value,
+                                    v_stride, ta, sx, sl, s_action, nullptr);
 }
 
 // The rollout tail of step t fused with the conv tower of step t + 1 (the
@@ -209,16 +295,16 @@ struct NextTower {
   const char* prep;
   uint32_t *m1, *m2, *m3;
 };
-template <int NZ, int C3, bool H16>
+template <int NZ, int C3, bool H16, class Env = SynthEnv>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void rollout_tail_tower_kernel(
     const float* part, int nz, const float* b4, float* a4, long long a4_stride, int B,
     const float* wpi, const float* bpi, const float* wv, const float* bv, int A, float* logits,
-    long long l_stride, float* value, long long v_stride, TailArgs ta, NextTower nt) {
+    long long l_stride, float* value, long long v_stride, typename Env::Args ta, NextTower nt) {
   __shared__ __attribute__((aligned(16))) char lds[kTowLds + kTowScr];
   float* sx = reinterpret_cast<float*>(lds + kTowObs);
   int* s_action = reinterpret_cast<int*>(sx + 512 + kMaxHeads);
-  rollout_tail_body<NZ>(part, nz, b4, a4, a4_stride, B, wpi, bpi, wv, bv, A, logits, l_stride, value, v_stride,
-                        ta, sx, sx + 512, *s_action, reinterpret_cast<uint4*>(lds));
+  rollout_tail_body<NZ, false, Env>(part, nz, b4, a4, a4_stride, B, wpi, bpi, wv, bv, A, logits, l_stride, value,
+                                    v_stride, ta, sx, sx + 512, *s_action, reinterpret_cast<uint4*>(lds));
   __syncthreads();  // the image in LDS; the tail's scratch free again
   tower_body<C3, H16, true>(nullptr, 0, nt.b1, nt.b2, nt.b3, nt.a1, nt.a2, nt.a3, nt.st, nt.prep, nt.m1, nt.m2,
                             nt.m3, lds, blockIdx.x);
@@ -229,17 +315,18 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void r
 // tower needs, the post-step state into pend) and then part j of the next
 // step's conv tower.  The pending states are committed by the next step's fc4
 // launch (fc4_roll_kernel: env_commit_pending), the first launch after this one.
-template <int NZ, int C3, bool H16>
+template <int NZ, int C3, bool H16, class Env = SynthEnv>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void rollout_tail_split_kernel(
     const float* part, int nz, const float* b4, float* a4, long long a4_stride, int B,
     const float* wpi, const float* bpi, const float* wv, const float* bv, int A, float* logits,
-    long long l_stride, float* value, long long v_stride, TailArgs ta, NextTower nt, PendState* pend) {
+    long long l_stride, float* value, long long v_stride, typename Env::Args ta, NextTower nt,
+    typename Env::Pend* pend) {
   __shared__ __attribute__((aligned(16))) char lds[kSpLds];
   const int n = blockIdx.x / kSplitParts, j = blockIdx.x - n * kSplitParts;
   float* sx = reinterpret_cast<float*>(lds + kSpImg);  // the tail's scratch in the a1 image
   int* s_action = reinterpret_cast<int*>(sx + 512 + kMaxHeads);
-  rollout_tail_body<NZ, true>(part, nz, b4, a4, a4_stride, B, wpi, bpi, wv, bv, A, logits, l_stride, value,
-                              v_stride, ta, sx, sx + 512, *s_action, reinterpret_cast<uint4*>(lds), n, j, pend);
+  rollout_tail_body<NZ, true, Env>(part, nz, b4, a4, a4_stride, B, wpi, bpi, wv, bv, A, logits, l_stride, value,
+                                   v_stride, ta, sx, sx + 512, *s_action, reinterpret_cast<uint4*>(lds), n, j, pend);
   __syncthreads();  // the image rows in LDS; the tail's scratch free again
   tower_part_body<C3, H16>(j, nt.b1, nt.b2, nt.b3, nt.a1, nt.a2, nt.a3, nt.st, nt.prep, nt.m1, nt.m2, nt.m3, lds, n);
 }
@@ -391,11 +478,11 @@ struct HeadArgs {
 // ---------------------------------------------------------------------------
 // forward
 // ---------------------------------------------------------------------------
-template <int C3>
+template <int C3, class Env = SynthEnv>
 static int forward_impl(const Layout& L, const float* P, const uint8_t* obs,
                         long long img_stride, int B, const acmi_acts_t* a,
                         int want_value, long long act_img_stride,
-                        hipStream_t s, const TailArgs* tail = nullptr, const void* prep = nullptr) {
+                        hipStream_t s, const typename Env::Args* tail = nullptr, const void* prep = nullptr) {
   // act_img_stride: images between consecutive batch rows in the activation
   // buffers (1 = contiguous; T = rollout step t of an env-major buffer).
   const long long st = act_img_stride;
@@ -489,21 +576,18 @@ static int forward_impl(const Layout& L, const float* P, const uint8_t* obs,
   fc4_plan(B, K4, &nz, &chunk);
   const bool split = nz > 1 && a->ws && a->ws_floats >= (long long)nz * (B + 1) * 512;
   const char* w4p = prep ? static_cast<const char*>(prep) + TowerPrep<C3>::BYTES + CT2::BYTES : nullptr;
-  // the split rollout step's pending env states, after fc4's slabs in the forward
-  // workspace (acmi_forward_ws_floats reserves them at B <= kSplitMaxB); only with
-  // the rollout fc4 kernel, the one launch that commits them
+  // the split rollout step's pending env states (Env::pend_area: after fc4's slabs in
+  // the forward workspace, or the caller's buffer); only with the rollout fc4 kernel,
+  // the one launch that commits them
   const bool fc4_roll = split && g_gemm_mode == ACMI_GEMM_X3 && w4p && fc4_roll_ok(a->a3, st * K4, K4, chunk);
-  PendState* pend = fc4_roll && tail && B <= kSplitMaxB &&
-                            a->ws_floats >= (long long)nz * (B + 1) * 512 + (long long)B * (sizeof(PendState) / 4)
-                        ? reinterpret_cast<PendState*>(a->ws + (long long)nz * (B + 1) * 512)
-                        : nullptr;
+  typename Env::Pend* pend = fc4_roll && tail && B <= kSplitMaxB ? Env::pend_area(*tail, a, nz, B) : nullptr;
   if (split) {
     // small (rollout) batches: split K over chunks; the heads kernel reduces
     // the slabs in fixed order and applies bias + relu
     // every rollout step with a pending area commits the entries flagged there
     // (the previous fused step's; also, at step 0, those a rollout abandoned
     // between fused steps left behind -- the flag is cleared on commit)
-    const Fc4Commit cm{pend, tail ? tail->io.state : acmi_env_state_t{}, pend ? B : 0};
+    const typename Env::Commit cm = Env::commit(tail, pend, B);
     if (!(fc4_roll &&
           launch_fc4_roll(a->a3, st * K4, B, K4, w4p, nz, chunk, a->ws,
                           reinterpret_cast<const unsigned*>(static_cast<const char*>(prep) + TowerPrep<C3>::HDR),
@@ -532,11 +616,12 @@ static int forward_impl(const Layout& L, const float* P, const uint8_t* obs,
     auto fused = [&](auto half) {  // with pending states the split form, at its one count
       constexpr bool H16 = decltype(half)::value;
       if constexpr (NZ == small_count(C3))
-        if (pend) return ha.launch<rollout_tail_split_kernel<NZ, C3, H16>>(dim3(B * kSplitParts), s, *tail, ntw, pend);
-      ha.launch<rollout_tail_tower_kernel<NZ, C3, H16>>(dim3(B), s, *tail, ntw);
+        if (pend)
+          return ha.launch<rollout_tail_split_kernel<NZ, C3, H16, Env>>(dim3(B * kSplitParts), s, *tail, ntw, pend);
+      ha.launch<rollout_tail_tower_kernel<NZ, C3, H16, Env>>(dim3(B), s, *tail, ntw);
     };
     if (!tail) ha.launch<heads_kernel<NZ>>(dim3(cdiv(B, 4)), s);
-    else if (!fuse_next) ha.launch<rollout_tail_kernel<NZ>>(dim3(B), s, *tail);
+    else if (!fuse_next) ha.launch<rollout_tail_kernel<NZ, Env>>(dim3(B), s, *tail);
     else if constexpr (fused_count(C3, NZ)) h16 ? fused(std::true_type{}) : fused(std::false_type{});
   });
   ACMI_REQUIRE(launched, ACMI_ERR_ARG, "fc4 split factor %d out of range", nz);
@@ -553,10 +638,11 @@ static bool spans32(long long rows, long long stride, long long per_row) {
   return rows <= 0 || (rows - 1) * stride + per_row < (1LL << 31);
 }
 
+template <class Env = SynthEnv>
 static int forward_dispatch(const acmi_net_t* net, const uint8_t* obs, int64_t img_stride,
                             int B, const acmi_acts_t* acts, int want_value,
                             long long act_stride, acmi_stream_t stream,
-                            const TailArgs* tail = nullptr) {
+                            const typename Env::Args* tail = nullptr) {
   Layout L;
   ACMI_REQUIRE(net && acts && obs && net->params, ACMI_ERR_ARG, "acmi_forward: null argument");
   ACMI_REQUIRE(make_layout(net->num_actions, net->conv3_filters, &L), ACMI_ERR_ARG,
@@ -573,10 +659,10 @@ static int forward_dispatch(const acmi_net_t* net, const uint8_t* obs, int64_t i
   if (B == 0) return ACMI_OK;
   hipStream_t s = (hipStream_t)stream;
   if (L.C3 == 32)
-    return forward_impl<32>(L, net->params, obs, img_stride, B, acts, want_value, act_stride, s, tail,
-                            net->conv_prep);
-  return forward_impl<64>(L, net->params, obs, img_stride, B, acts, want_value, act_stride, s, tail,
-                          net->conv_prep);
+    return forward_impl<32, Env>(L, net->params, obs, img_stride, B, acts, want_value, act_stride, s, tail,
+                                 net->conv_prep);
+  return forward_impl<64, Env>(L, net->params, obs, img_stride, B, acts, want_value, act_stride, s, tail,
+                               net->conv_prep);
 }
 
 }  // namespace acmi

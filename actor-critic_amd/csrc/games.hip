@@ -18,15 +18,6 @@
 
 namespace acmi {
 
-// The game of env n of the call, in two halves so that the load can be issued with the
-// other state reads and waited for with them: game_byte is the load, game_of moves the
-// wave-uniform value to a scalar register (a byte load has no scalar form), so every
-// branch on the id stays a scalar branch.
-__device__ __forceinline__ int game_byte(const uint8_t* games, int n) { return games ? (int)games[n] : 0; }
-__device__ __forceinline__ int game_of(const uint8_t* games, int byte, int fallback) {
-  return games ? __builtin_amdgcn_readfirstlane(byte) : fallback;
-}
-
 // A bad env's reset (games.hip, top): the whole block takes this path or none does.
 __device__ __forceinline__ void game_bad_env(uint8_t* obs, int32_t* bad_envs) {
   uint4* out = reinterpret_cast<uint4*>(obs);
@@ -71,88 +62,12 @@ __global__ __launch_bounds__(kGameThreads) void game_step_kernel(
     uint32_t seed, const int32_t* actions, const uint8_t* obs_in, long long in_stride, uint8_t* obs_out,
     long long out_stride, float* rewards, uint8_t* terminals, uint8_t* truncated, float* ep_rewards, long long ld) {
   const int n = blockIdx.x;
-  const uint32_t e = (uint32_t)(env_offset + n);
-  // the env's game ahead of every other load: loads return in order, so the wait for
-  // this byte after the barrier then leaves the stack words in flight
-  const int gbyte = kPerEnv ? game_byte(games, n) : 0;
-  // the previous stack's words next, all of a thread's at once: they do not
-  // depend on the action, and a load per loop iteration would wait out one
-  // memory latency per iteration (stepper.hpp env_prefetch)
-  const uint4* in = reinterpret_cast<const uint4*>(obs_in + (long long)n * in_stride);
-  uint4 old[kGameWords];
-#pragma unroll
-  for (int i = 0; i < kGameWords; ++i) {
-    const int g = threadIdx.x + kGameThreads * i;
-    old[i] = in[g < kGameFrameWords ? g : 0];
-  }
-  const uint8_t was = st.done[n];
-  const bool was_done = was != kRunning;
-  int32_t k = st.episode[n];
-  int32_t t = st.step[n];
-  float total = st.total[n];
-  int32_t* vars = st.vars + (long long)n * kGameInts;
-  GameVars v = game_load(vars);
+  const GameCall c{st, games, bad_envs, rules, seed};
+  GamePre pre;
+  game_prefetch<kPerEnv>(c, n, obs_in + (long long)n * in_stride, pre);
   const uint32_t action = (uint32_t)actions[n];
-  __syncthreads();  // everyone's state reads before thread 0's state writes
-  const int game = kPerEnv ? game_of(games, gbyte, st.game) : st.game;
-  // A bad env is not branched around (an early exit lets the compiler sink the state
-  // loads below the barrier, behind the wait for the id): it steps as some game in
-  // registers, and only what is stored differs.
-  const bool bad = kPerEnv && (uint32_t)game >= (uint32_t)kNumDeviceGames;
-  if (was == kGameOver) {  // _AutoResetWrapper: reset lazily at the next step
-    k += 1;
-    t = 0;
-    total = 0.f;
-    game_start(game, seed, e, (uint32_t)k, v);
-  }
-  // the reset frame's state, read only if was_done; after a lost life (kLifeLost) the
-  // game goes on in place and the stack restarts from the respawned ball's frame
-  const GameView first = game_view(game, v);
-  t += 1;
-  float rew;
-  bool own, lost;
-  game_advance(game, seed, e, (uint32_t)k, action, v, rew, own, lost);
-  const GameCut cut = game_cut(game, rules.episodic_life, rules.max_steps, t, own, lost);
-  const bool term = cut.term;
-  const GameView now = game_view(game, v);
-  uint4* out = reinterpret_cast<uint4*>(obs_out + (long long)n * out_stride);
-#pragma unroll
-  for (int i = 0; i < kGameWords; ++i) {
-    const int g = threadIdx.x + kGameThreads * i;
-    if (g >= kGameFrameWords) break;
-    uint4 o = old[i];
-    if (was_done) {  // FrameStackWrapper.reset: the reset frame repeated 4x
-      const uint4 r = game_word(first, g);
-      o = make_uint4(r.x * 0x01010101u, r.y * 0x01010101u, r.z * 0x01010101u, r.w * 0x01010101u);
-    }
-    const uint4 p = game_word(now, g);
-    // np.roll(stack, -1, axis=-1); zero-fill on terminal; last channel = frame
-    o.x = (term ? 0u : (o.x >> 8)) | (p.x << 24);
-    o.y = (term ? 0u : (o.y >> 8)) | (p.y << 24);
-    o.z = (term ? 0u : (o.z >> 8)) | (p.z << 24);
-    o.w = (term ? 0u : (o.w >> 8)) | (p.w << 24);
-    if (bad) o = make_uint4(0u, 0u, 0u, 0u);
-    out[g] = o;
-  }
-  if (threadIdx.x == 0 && bad) {
-    rewards[n * ld] = 0.f;
-    terminals[n * ld] = 0;
-    if (truncated) truncated[n * ld] = 0;
-    ep_rewards[n * ld] = __int_as_float(0x7fc00000);
-    if (bad_envs) atomicAdd(bad_envs, 1);
-  } else if (threadIdx.x == 0) {
-    total += rew;
-    rewards[n * ld] = rew;
-    terminals[n * ld] = term ? 1 : 0;
-    if (truncated) truncated[n * ld] = cut.trunc ? 1 : 0;
-    // EpisodeInfoWrapper sits inside the life cut: whole-game totals, at a game over only
-    ep_rewards[n * ld] = cut.over ? total : __int_as_float(0x7fc00000);
-    st.episode[n] = k;
-    st.step[n] = t;
-    st.total[n] = cut.over ? 0.f : total;
-    st.done[n] = cut.over ? kGameOver : (term ? kLifeLost : kRunning);
-    game_store(vars, v);
-  }
+  game_step_block_pre<kPerEnv>(c, n, (uint32_t)(env_offset + n), action, pre, obs_out + (long long)n * out_stride,
+                               GameOut{rewards, terminals, truncated, ep_rewards, ld});
 }
 
 static void launch_game_step(const acmi_game_state_t& st, const uint8_t* games, int32_t* bad_envs,

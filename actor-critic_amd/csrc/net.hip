@@ -900,6 +900,40 @@ int acmi_rollout_step_masked(const acmi_net_t* net, const uint8_t* obs, int64_t 
   return rollout_step_impl(net, obs, img_stride, B, acts, act_img_stride, io, legal, stream);
 }
 
+int acmi_game_pend_ints(void) { return (int)(sizeof(GamePend) / 4); }
+int64_t acmi_rollout_game_io_bytes(void) { return (int64_t)sizeof(acmi_rollout_game_io_t); }
+
+int acmi_rollout_step_games(const acmi_net_t* net, const uint8_t* obs, int64_t img_stride, int B,
+                            const acmi_acts_t* acts, int64_t act_img_stride, const acmi_rollout_game_io_t* gio,
+                            const uint32_t* legal, acmi_stream_t stream) {
+  ACMI_REQUIRE(net_modes_ok(net), ACMI_ERR_ARG, "acmi_rollout_step_games: bad acmi_net_t mode fields");
+  const ModeScope mode_scope(net);
+  ACMI_REQUIRE(net && gio, ACMI_ERR_ARG, "acmi_rollout_step_games: null net / io");
+  const acmi_rollout_io_t* io = &gio->io;
+  ACMI_REQUIRE(io->actions && io->bad_rows && io->obs_out && io->rewards && io->terminals && io->episode_rewards &&
+                   io->ld >= 1 && io->out_stride >= 84 * 84 * 4 && io->out_stride % 16 == 0 &&
+                   img_stride % 16 == 0 && io->row_offset >= 0 && io->env_offset >= 0,
+               ACMI_ERR_ARG, "acmi_rollout_step_games: bad arguments");
+  const acmi_game_state_t& gs = gio->state;
+  ACMI_REQUIRE(gs.episode && gs.step && gs.total && gs.done && gs.vars && gs.game >= 0 && gs.game < kNumDeviceGames,
+               ACMI_ERR_ARG, "acmi_rollout_step_games: bad game state (null array or no such game)");
+  ACMI_REQUIRE((gio->rules.episodic_life == 0 || gio->rules.episodic_life == 1) && gio->rules.max_steps >= 0 &&
+                   gio->rules.max_steps <= BREAKOUT_MAX_STEPS,
+               ACMI_ERR_ARG, "acmi_rollout_step_games: rules: episodic_life 0 or 1, max_steps 0..2000");
+  ACMI_REQUIRE(net->num_actions < kMaxHeads, ACMI_ERR_ARG,
+               "acmi_rollout_step_games: num_actions=%d, the fused step takes at most %d; step wider action sets "
+               "with acmi_forward_strided + acmi_sample_actions_dev + acmi_game_step_mixed",
+               net->num_actions, kMaxHeads - 1);
+  ACMI_REQUIRE(B > kSplitMaxB || !(io->next_acts || io->tower_done) || gio->pend, ACMI_ERR_ARG,
+               "acmi_rollout_step_games: the split form (B <= %d with step fusion) needs the pending area",
+               kSplitMaxB);
+  ACMI_REQUIRE((uintptr_t)gio->pend % 16 == 0, ACMI_ERR_ARG, "acmi_rollout_step_games: pend must be 16-byte aligned");
+  GameTailArgs ta{*io, obs, (long long)img_stride, legal,
+                  GameCall{gs, gio->games, gio->bad_envs, gio->rules, io->env_seed}, gio->truncated,
+                  reinterpret_cast<GamePend*>(gio->pend)};
+  return forward_dispatch<GameEnv>(net, obs, img_stride, B, acts, 1, act_img_stride, stream, &ta);
+}
+
 int64_t acmi_forward_ws_floats(int B) {
   if (B <= 0) return 0;
   int nz, chunk;

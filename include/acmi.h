@@ -903,6 +903,57 @@ int acmi_rollout_step_masked(const acmi_net_t* net, const uint8_t* obs,
                              const uint32_t* legal, acmi_stream_t stream);
 
 /* ------------------------------------------------------------------------
+ * The fused rollout step for the device games: acmi_rollout_step[_masked] with
+ * acmi_game_step_mixed in place of acmi_env_step -- the same two launch groups,
+ * the same kernels with the games' step in their tail.  Bit-identical to
+ * acmi_forward_strided + acmi_sample_actions_dev[_masked] + acmi_game_step_mixed
+ * (state arrays, truncations and bad_envs included).
+ *   io         as for acmi_rollout_step (row_offset, env_offset, env_seed, ld,
+ *              tower_done / next_acts / next_act_stride / obs_copy and the
+ *              num_actions <= 31 limit unchanged); io.state is ignored.
+ *   state      the game state, pointers at batch row 0's env.
+ *   games      one byte per env of the call, nullable (state.game for all).
+ *   rules      as for acmi_game_step_cuts; {0, 0} gives acmi_game_step's step.
+ *   truncated  nullable; element b at [b*io.ld], like the terminals.
+ *   bad_envs   nullable; a bad env (games[b] >= acmi_game_count()) keeps its
+ *              state, gets a zero stack (the next tower runs on zeros), reward
+ *              0, terminal 0, truncated 0, a NaN episode reward, and is counted
+ *              once per step.
+ *   pend       the pending area of the split form, B * acmi_game_pend_ints()
+ *              int32, 16-byte aligned, zeroed before its first step.  At B <= 64
+ *              a step with next_acts leaves each env's post-step state (episode,
+ *              step, total, done code, vars and a flag) there, and the NEXT
+ *              step's fc4 launch commits the flagged entries into `state`; so
+ *              every step of such a rollout passes the same pend, the rollout
+ *              ends with an unfused-tower step (next_acts = NULL, tower_done =
+ *              1), and a caller that re-initialises `state` (acmi_game_reset*)
+ *              zeroes pend as well, or a stale entry would be committed over the
+ *              reset state.  It is NOT in acts->ws: acmi_forward_ws_floats is
+ *              unchanged.  Required (ACMI_ERR_ARG) at B <= 64 with next_acts or
+ *              tower_done set; unused above 64.
+ * legal: nullable; as in acmi_rollout_step_masked (then num_actions <= 32 holds
+ * anyway).  NULL pointers among the required ones, rules or state.game out of
+ * range, num_actions > 31, a missing or misaligned pend: ACMI_ERR_ARG before
+ * anything is enqueued.  B = 0: ACMI_OK, nothing launched.  The struct's size:
+ * acmi_rollout_game_io_bytes() (it is not among acmi_abi_struct_sizes' five).
+ * ---------------------------------------------------------------------- */
+typedef struct acmi_rollout_game_io {
+  acmi_rollout_io_t io;
+  acmi_game_state_t state;
+  const uint8_t* games;
+  acmi_game_rules_t rules;
+  uint8_t* truncated;
+  int32_t* bad_envs;
+  int32_t* pend;
+} acmi_rollout_game_io_t;
+int acmi_game_pend_ints(void);
+int64_t acmi_rollout_game_io_bytes(void);
+int acmi_rollout_step_games(const acmi_net_t* net, const uint8_t* obs,
+                            int64_t img_stride, int B, const acmi_acts_t* acts,
+                            int64_t act_img_stride, const acmi_rollout_game_io_t* io,
+                            const uint32_t* legal, acmi_stream_t stream);
+
+/* ------------------------------------------------------------------------
  * Building blocks exposed for parity tests and the bench (not needed by a
  * reference-shaped caller).
  * ---------------------------------------------------------------------- */

@@ -12,7 +12,10 @@
   iter   the unfused 32 x 5 A2C iteration (rollout + update, a host clock around a device
          synchronise) on catch against the synthetic stepper forced onto the same
          unfused path (ACMI_ROLLOUT_FUSED=0), and the synthetic stepper's default
-         (fused) path for scale; ms per iteration per round.
+         (fused) path for scale; ms per iteration per round.  --env mixed is the
+         catch+breakout batch; --fused puts the games on the rollout's fused step
+         (DeviceGameEnvs(fused_step=True)) -- run it against the same command without it,
+         in fresh processes in alternating order.
 """
 import argparse
 import json
@@ -96,8 +99,9 @@ def cmd_iter(args):
     from actorcritic.objectives import A2CObjective
     sess.reset_default_graph()
     N, T = args.envs, args.steps
-    if args.env == 'catch':
-        env = MultiEnv(DeviceGameEnvs('catch', N, seed=1))
+    if args.env in ('catch', 'mixed'):
+        kw = {'fused_step': True} if args.fused else {}  # (an older DeviceGameEnvs has no such keyword)
+        env = MultiEnv(DeviceGameEnvs('catch' if args.env == 'catch' else 'catch+breakout', N, seed=1, **kw))
     else:
         env = MultiEnv(SyntheticAtariEnvs(N, num_actions=3, seed=1))
     model = AtariModel(env.observation_space, env.action_space, 64, random_seed=1)
@@ -143,7 +147,8 @@ def main():
                     help='leave the mixed case out (an older libacmi under ACMI_LIB has no acmi_game_step_mixed)')
     st.set_defaults(fn=cmd_step)
     it = sub.add_parser('iter')
-    it.add_argument('--env', choices=('catch', 'synthetic-unfused', 'synthetic'), default='catch')
+    it.add_argument('--env', choices=('catch', 'mixed', 'synthetic-unfused', 'synthetic'), default='catch')
+    it.add_argument('--fused', action='store_true', help='catch / mixed: the fused rollout step')
     it.add_argument('--envs', type=int, default=32)
     it.add_argument('--steps', type=int, default=5)
     it.add_argument('--iters', type=int, default=500)

@@ -50,6 +50,7 @@ def run(args, seed, emit):
     num_actions = 18 if args.mask_actions else (4 if mixed else None)
     episodes = lambda g: args.breakout_episodes if (mixed and g == 'breakout') else E
     rules = dict(episodic_life=args.episodic_life, max_episode_steps=args.max_episode_steps)
+    fused = dict(fused_games=args.fused_games)
 
     def stats(returns):
         r = returns.double().flatten()
@@ -93,11 +94,11 @@ def run(args, seed, emit):
 
     if args.algo == 'ppo':
         train_ppo(args.game, N, T, None, args.game, max_updates=args.updates, seed=seed, game=args.game,
-                  on_update=on_update, mask_actions=args.mask_actions, normalize_returns=norm, **rules)
+                  on_update=on_update, mask_actions=args.mask_actions, normalize_returns=norm, **rules, **fused)
     else:
         train_a2c_acktr(args.algo == 'acktr', args.game, N, T, None, args.game, max_updates=args.updates, seed=seed,
                         game=args.game, on_update=on_update, mask_actions=args.mask_actions,
-                        normalize_returns=norm, **rules)
+                        normalize_returns=norm, **rules, **fused)
 
 
 def main():
@@ -119,6 +120,8 @@ def main():
     ap.add_argument('--max-episode-steps', type=int, default=None, help='step cap (truncation), 1..2000')
     ap.add_argument('--normalize-returns', action='store_true',
                     help='scale rewards by the running std of the discounted return, per game')
+    ap.add_argument('--fused-games', action='store_true',
+                    help='train through the rollout\'s fused step (DeviceGameEnvs(fused_step=True))')
     ap.add_argument('--out', default=None, help='also append the JSON lines to this file')
     args = ap.parse_args()
     if args.mask_actions and args.eval_envs != args.envs:
