@@ -314,6 +314,52 @@ class MultiEnvAgent(Agent):
         rb.episode_rewards.copy_(hb.episode_rewards, non_blocking=True)
         return self._batch(eng, rb, N, T)
 
+    # -- run state -----------------------------------------------------
+    def _stateful_env(self):
+        """The batched device env whose state a run state holds; ValueError for the others."""
+        if not self._fast():
+            raise ValueError('a run state needs a batched device env: the list path keeps its state in host envs')
+        env = self._env.batched
+        if getattr(env, 'host_stepped', False) or not hasattr(env, 'state_dict'):
+            raise ValueError('{} has no run state: host-stepped envs keep their state in the host envs'
+                             .format(type(env).__name__))
+        return env
+
+    def run_state(self):
+        """What the next ``interact()`` reads beside the model, between two complete rollouts:
+        ``{'next_obs': [N,84,84,4] u8, 'sample_counter': int, 'env': the batched env's
+        state_dict()}``, CPU tensors and plain ints.  Waits for the engine's stream (and the
+        side stream of the two-halves form).  ValueError before the first ``interact()`` and
+        for host-stepped or list-path envs.  The rollout length is not part of it."""
+        env = self._stateful_env()
+        rb = self._bufs
+        if self._observations is None or rb is None:
+            raise ValueError('run_state() before the first interact(): the envs have not been reset')
+        eng = self._model.engine
+        torch.cuda.current_stream(eng.device).synchronize()
+        if rb.side is not None:
+            rb.side.synchronize()
+        return {'next_obs': rb.next_obs.detach().cpu().clone(), 'sample_counter': int(eng.sample_counter),
+                'env': env.state_dict()}
+
+    def load_run_state(self, state):
+        """Continues from a ``run_state()``: fills ``next_obs`` (making the rollout buffers for
+        (N, this agent's T) if need be) and marks the envs as reset, so that no ``reset_into``
+        follows; sets the engine's ``sample_counter``; loads the env state (ValueError when the
+        envs are not the saved ones).  Load the model checkpoint first (checkpoint.load)."""
+        env = self._stateful_env()
+        eng = self._model.engine
+        N, T = env.num_envs, self._num_steps
+        nxt = state['next_obs']
+        if not torch.is_tensor(nxt) or tuple(nxt.shape) != (N, 84, 84, 4) or nxt.dtype != torch.uint8:
+            raise ValueError('run state: next_obs is not the [{}, 84, 84, 4] uint8 stacks of these envs'.format(N))
+        env.load_state_dict(state['env'])
+        if self._bufs is None or self._bufs.N != N or self._bufs.T != T:
+            self._bufs = _RolloutBuffers(eng, N, T, env)
+        self._bufs.next_obs.copy_(nxt.to(eng.device))
+        self._observations = self._bufs.next_obs
+        eng.sample_counter = int(state['sample_counter'])
+
     def _batch(self, eng, rb, N, T):
         """interact()'s 6-tuple from the rollout buffers, registered for the update."""
         from actorcritic.envs.atari.model import ForwardOut

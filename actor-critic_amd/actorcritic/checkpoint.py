@@ -6,6 +6,11 @@ TF checkpoints are unreadable without TensorFlow, so this engine writes its own:
 ``torch.load(weights_only=True)``) and a ``checkpoint`` index file naming the latest,
 like TF's.  Summaries are JSON lines (step, policy_loss, baseline_loss,
 policy_entropy, episode_reward).
+
+Beside a model checkpoint every rank may write its RUN STATE, ``<prefix>-<step>.run<rank>.pt``
+(``save_run_state`` / ``load_run_state``): the envs' state, the next observations, the sample
+counter and the return normaliser's carry -- with it a run on the device envs resumes bit for
+bit.  The model checkpoint and the index file are what they were without it.
 """
 
 import json
@@ -47,7 +52,8 @@ def _normalizer(objective):
 
 def save(prefix, step, model, optimizer=None, objective=None):
     """``objective``: with a ReturnNormalizer its stats and settings are stored under retnorm/
-    (not the envs' running returns: env state is not checkpointed)."""
+    (not the envs' running returns: per-env state is not in this file but in the run state,
+    ``save_run_state``)."""
     path = '{}-{}.pt'.format(prefix, int(step))
     blob = {'params': model.params.detach().cpu(), 'global_step': torch.tensor(int(step)),
             'num_actions': torch.tensor(model.num_actions), 'conv3_filters': torch.tensor(model.conv3_num_filters)}
@@ -78,7 +84,8 @@ def latest(directory):
 
 def load(path, model, optimizer=None, global_step=None, objective=None):
     """``objective``: its ReturnNormalizer takes the retnorm/ entries when the file has them
-    (a checkpoint written without them leaves it as it is)."""
+    (a checkpoint written without them leaves it as it is); its carry is zeroed, so a resume
+    that continues the run loads the run state AFTER this (``load_run_state``)."""
     blob = torch.load(path, map_location='cpu', weights_only=True)
     if int(blob['num_actions']) != model.num_actions or int(blob['conv3_filters']) != model.conv3_num_filters:
         raise ValueError('checkpoint was written for a different model')
@@ -104,6 +111,63 @@ def load(path, model, optimizer=None, global_step=None, objective=None):
     if norm is not None and 'retnorm/stats' in blob:
         norm.load_state_dict({'stats': blob['retnorm/stats'], 'epsilon': float(blob['retnorm/epsilon']),
                               'clip': float(blob['retnorm/clip'])})
+    return blob
+
+
+# -- run state: what the rollout side carries from one update to the next --------
+RUN_STATE_FORMAT = 1
+
+
+def run_state_path(prefix, step, rank):
+    """``<prefix>-<step>.run<rank>.pt``: rank ``rank``'s run state beside the model checkpoint
+    ``<prefix>-<step>.pt``."""
+    return '{}-{}.run{}.pt'.format(prefix, int(step), int(rank))
+
+
+def save_run_state(prefix, step, agent, objective=None):
+    """Called by EVERY rank, between an update and the next ``interact()``: writes this rank's
+    ``agent.run_state()`` (next observations, sample counter, env state) and, with a
+    ReturnNormalizer on ``objective``, its ``carry`` to ``run_state_path(prefix, step, rank)``.
+    Tensors, ints and dicts of them only (``torch.load(weights_only=True)``); ``format``,
+    ``rank``, ``world_size`` and ``global_step`` say what the file is.  Neither the model
+    checkpoint nor the ``checkpoint`` index is touched."""
+    from actorcritic import parallel
+    rank, world = int(parallel.rank()), int(parallel.world_size())
+    blob = {'format': RUN_STATE_FORMAT, 'rank': rank, 'world_size': world, 'global_step': int(step)}
+    blob.update(agent.run_state())
+    norm = _normalizer(objective)
+    if norm is not None:
+        blob['retnorm/carry'] = norm.carry_state()
+    path = run_state_path(prefix, step, rank)
+    tmp = path + '.tmp'
+    torch.save(blob, tmp)
+    os.replace(tmp, path)
+    return path
+
+
+def load_run_state(path, agent, objective=None):
+    """Continues ``agent`` (and ``objective``'s ReturnNormalizer) from a ``save_run_state`` file.
+    Call it AFTER ``load``: loading a model checkpoint zeroes the normalizer's carry.  ValueError
+    when the file is another rank's or another world size's (the env shards would differ), of
+    another format, or lacks the carry a normalizer needs; and whatever
+    ``agent.load_run_state`` refuses.  -> the blob (``global_step``: the step it was saved at)."""
+    from actorcritic import parallel
+    blob = torch.load(path, map_location='cpu', weights_only=True)
+    if int(blob.get('format', -1)) != RUN_STATE_FORMAT:
+        raise ValueError('{}: run state format {}, this build reads {}'.format(path, blob.get('format'),
+                                                                               RUN_STATE_FORMAT))
+    rank, world = int(parallel.rank()), int(parallel.world_size())
+    if int(blob['world_size']) != world:
+        raise ValueError('{}: run state of a world_size of {}, this job has {}'.format(path, int(blob['world_size']),
+                                                                                     world))
+    if int(blob['rank']) != rank:
+        raise ValueError('{}: run state of rank {}, this is rank {}'.format(path, int(blob['rank']), rank))
+    norm = _normalizer(objective)
+    if norm is not None and 'retnorm/carry' not in blob:
+        raise ValueError('{}: no retnorm/carry for the objective\'s ReturnNormalizer'.format(path))
+    agent.load_run_state({k: blob[k] for k in ('next_obs', 'sample_counter', 'env')})
+    if norm is not None:
+        norm.load_carry(blob['retnorm/carry'])
     return blob
 
 

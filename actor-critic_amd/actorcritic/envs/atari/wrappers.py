@@ -183,8 +183,51 @@ class EpisodeInfoWrapper(Wrapper):
         return rewards
 
 
+# ``kind`` of a batched env's state_dict (ints: the dict holds tensors and plain ints only)
+ENV_KIND_SYNTHETIC, ENV_KIND_GAMES = 1, 2
+_ENV_IDENTITY = ('kind', 'num_envs', 'env_offset', 'seed', 'num_actions', 'game_ids', 'episodic_life',
+                 'max_episode_steps')
+
+
+def check_env_identity(state, identity):
+    """ValueError naming the first field of ``identity`` (what a batched env is: ints, and the
+    int64 [N] game ids) that the saved ``state`` does not share."""
+    for field in _ENV_IDENTITY:
+        if field not in identity:
+            continue
+        want, got = identity[field], state.get(field)
+        if torch.is_tensor(want):
+            same = torch.is_tensor(got) and got.shape == want.shape and torch.equal(got.to(want.dtype).cpu(), want)
+            shown = lambda t: t.tolist() if torch.is_tensor(t) and t.numel() <= 16 else type(t).__name__
+        else:
+            same = isinstance(got, int) and got == want
+            shown = lambda v: v
+        if not same:
+            raise ValueError('env state was saved with {} = {}, these envs have {}'.format(field, shown(got),
+                                                                                          shown(want)))
+
+
+def load_env_arrays(state, arrays):
+    """Copies the saved tensors into the env's own ({key: device tensor}); ValueError for a
+    missing key, another shape or another dtype."""
+    for key, dst in arrays.items():
+        src = state.get(key)
+        if not torch.is_tensor(src) or src.shape != dst.shape or src.dtype != dst.dtype:
+            raise ValueError('env state: {} is {}, expected {} {}'.format(
+                key, 'missing' if src is None else '{} {}'.format(tuple(getattr(src, 'shape', ())),
+                                                                   getattr(src, 'dtype', type(src).__name__)),
+                tuple(dst.shape), dst.dtype))
+    for key, dst in arrays.items():
+        dst.copy_(state[key].to(dst.device))
+
+
 class SyntheticAtariEnvs(object):
     """A batch of synthetic Atari games with frame stacking, on one GPU.
+
+    ``state_dict()`` / ``load_state_dict(d)``: everything the next step reads (the five per-env
+    state arrays and the gym-like API's stack), as CPU tensors, beside what the envs ARE (ints
+    and the per-env game ids); loading into envs built from other arguments is a ValueError
+    that names the field.  Part of an agent's run state (MultiEnvAgent.run_state).
 
     Args:
         num_envs: environments on this device.
@@ -285,6 +328,27 @@ class SyntheticAtariEnvs(object):
         self.step_into(a.data_ptr(), self._obs.data_ptr(), OBS_BYTES, self._obs.data_ptr(), OBS_BYTES,
                        rew.data_ptr(), term.data_ptr(), ep.data_ptr(), 1)
         return self._obs.clone(), rew, term.view(torch.bool), EpisodeInfoBatch(ep[:, None])
+
+    # -- run state ----------------------------------------------------------------
+    def _identity(self):
+        ids = torch.full((self.num_envs,), -1, dtype=torch.int64) if self.games is None \
+            else self.games.cpu().to(torch.int64)
+        return {'kind': ENV_KIND_SYNTHETIC, 'num_envs': self.num_envs, 'env_offset': self.env_offset,
+                'seed': self.seed, 'num_actions': int(self.action_space.n), 'game_ids': ids}
+
+    def _state_tensors(self):
+        return {'episode': self._episode, 'step': self._step, 'length': self._length, 'total': self._total,
+                'done': self._done, 'obs': self._obs}
+
+    def state_dict(self):
+        """(class docstring) -- CPU tensors and plain ints; waits for the device."""
+        out = self._identity()
+        out.update({k: v.detach().cpu().clone() for k, v in self._state_tensors().items()})
+        return out
+
+    def load_state_dict(self, state):
+        check_env_identity(state, self._identity())
+        load_env_arrays(state, self._state_tensors())
 
     def close(self):
         pass
@@ -524,6 +588,14 @@ class HostAtariEnvs(object):
         self.stack_into(p, OBS_BYTES, p, OBS_BYTES)
         dev = lambda a: torch.from_numpy(a).to(self.device)
         return self._obs.clone(), dev(rewards), dev(terminals), EpisodeInfoBatch(dev(episode_rewards)[:, None])
+
+    def state_dict(self):
+        """Always a ValueError: the emulator state lives in the host envs, which have no such
+        interface ("What is refused")."""
+        raise ValueError('HostAtariEnvs has no state_dict: the state of host-stepped envs lives in the host envs')
+
+    def load_state_dict(self, state):
+        self.state_dict()
 
     def close(self):
         for env in self._envs:

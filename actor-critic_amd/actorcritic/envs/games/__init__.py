@@ -19,7 +19,8 @@ import torch
 
 from actorcritic import _lib, _ops, spaces
 from actorcritic._engine import OBS_BYTES
-from actorcritic.envs.atari.wrappers import EpisodeInfoBatch, _mask_tensor, action_mask_bits
+from actorcritic.envs.atari.wrappers import (ENV_KIND_GAMES, EpisodeInfoBatch, _mask_tensor, action_mask_bits,
+                                             check_env_identity, load_env_arrays)
 from actorcritic.envs.games.host import (GAME_ACTIONS, GAMES, STATE_INTS, HostGame, check_max_episode_steps,
                                          env_game_ids, game_id, game_pattern)
 
@@ -69,6 +70,16 @@ class DeviceGameEnvs(object):
     one kernel per env), bit-identical to the default three-call chain; ``step_into``,
     ``step`` and :func:`evaluate` are unchanged.  The instance then owns the zeroed
     pending buffer of the split form (``_pend``), which ``reset_into`` clears.
+
+    ``state_dict()`` / ``load_state_dict(d)``: what the next step reads --
+    episode, step, total, done, vars, the gym-like API's stack, and ``bad_envs`` when mixed -- as
+    CPU tensors, beside what the envs ARE (kind, num_envs, env_offset, seed, num_actions, the
+    per-env game ids, episodic_life, max_episode_steps; ints and one int64 tensor).  Loading
+    into envs that differ in any of those is a ValueError naming the field.  ``fused_step`` is
+    free to differ: the fused step is bit-identical to the chain, so a state saved under one
+    resumes under the other.  Between two complete rollouts nothing is pending: ``state_dict``
+    checks that every ``_pend`` flag is zero (RuntimeError otherwise) and saves none of it;
+    loading zeroes ``_pend``, as ``reset_into`` does.
     """
 
     # Off unless asked for (the keyword): the rollout steps these envs through forward +
@@ -135,6 +146,10 @@ class DeviceGameEnvs(object):
             # launch; an entry is int32 x acmi_game_pend_ints(), a multiple of 16 bytes
             self._pend_ints = int(lib.acmi_game_pend_ints())
             self._pend = torch.zeros((N, self._pend_ints), dtype=torch.int32, device=self.device)
+            # an entry's flag word (games.hpp GamePend: k, t, total, done, vars[STATE_INTS], flag, 3 pads)
+            self._pend_flag = 4 + STATE_INTS
+            if self._pend_ints != self._pend_flag + 4:
+                raise ImportError('libacmi pending entry layout mismatch')
         self._obs = torch.zeros((N, 84, 84, 4), dtype=torch.uint8, device=self.device)
 
     def _stream(self):
@@ -234,6 +249,34 @@ class DeviceGameEnvs(object):
                        trunc_ptr=None if trunc is None else trunc.data_ptr())
         self.last_truncations = None if trunc is None else trunc.view(torch.bool)
         return self._obs.clone(), rew, term.view(torch.bool), EpisodeInfoBatch(ep[:, None])
+
+    # -- run state (class docstring) ----------------------------------------------
+    def _identity(self):
+        return {'kind': ENV_KIND_GAMES, 'num_envs': self.num_envs, 'env_offset': self.env_offset,
+                'seed': self.seed, 'num_actions': int(self.action_space.n),
+                'game_ids': torch.tensor([int(i) for i in self.env_game_ids], dtype=torch.int64),
+                'episodic_life': int(self.episodic_life), 'max_episode_steps': int(self.max_episode_steps or 0)}
+
+    def _state_tensors(self):
+        out = {'episode': self._episode, 'step': self._step, 'total': self._total, 'done': self._done,
+               'vars': self._vars, 'obs': self._obs}
+        if self.is_mixed:
+            out['bad_envs'] = self.bad_envs
+        return out
+
+    def state_dict(self):
+        if self.fused_step and bool(self._pend[:, self._pend_flag].any()):  # (one host read)
+            raise RuntimeError('a game state is still pending (a rollout was abandoned between two fused steps): '
+                               'the env state is whole only after a complete rollout or a reset')
+        out = self._identity()
+        out.update({k: v.detach().cpu().clone() for k, v in self._state_tensors().items()})
+        return out
+
+    def load_state_dict(self, state):
+        check_env_identity(state, self._identity())
+        load_env_arrays(state, self._state_tensors())
+        if self.fused_step:  # (as reset_into: a stale entry must never be committed over the loaded state)
+            self._pend.zero_()
 
     def close(self):
         pass

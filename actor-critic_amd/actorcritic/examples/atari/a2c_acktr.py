@@ -26,7 +26,7 @@ from actorcritic.session import Session, get_or_create_global_step, no_op
 def train_a2c_acktr(acktr, env_id, num_envs, num_steps, checkpoint_path, model_name, summary_path=None,
                     max_updates=None, seed=0, log_every=10, env_fns=None, mask_actions=False, game=None,
                     on_update=None, episodic_life=False, max_episode_steps=None, normalize_returns=False,
-                    fused_games=False):
+                    fused_games=False, run_state=False, checkpoint_every=100):
     """Trains an Atari model with A2C (RMSProp, conv3 64) or ACKTR (K-FAC, conv3 32).
 
     ``num_envs`` is per GPU; with WORLD_SIZE > 1 (torchrun) every rank steps its own shard.
@@ -53,10 +53,18 @@ def train_a2c_acktr(acktr, env_id, num_envs, num_steps, checkpoint_path, model_n
     (DeviceGameEnvs(fused_step=True)), bit-identical to the default three-call chain.
     ``checkpoint_path`` None: nothing is loaded or saved.  ``on_update(updates, model)`` is called
     after every update (learning curves: scripts/learn_games.py).
+    ``checkpoint_every`` (``--checkpoint-every K``): a checkpoint whenever the global step is a multiple of K.
+    ``run_state`` (``--run-state``), device envs only: every rank writes its run state
+    (checkpoint.save_run_state: env state, next observations, sample counter, the normaliser's carry) whenever
+    rank 0 writes a model checkpoint, and one more pair when the loop ends at ``max_updates`` or the last
+    step; at start the latest model checkpoint is loaded WITH this rank's run state (a missing file is a
+    ValueError, not a silent reset), and the run continues bit for bit.  A stop request then writes nothing:
+    it may fall between a rollout and its update, and the last pair stays the point to resume from.
     """
     parallel.init_from_env()
     if game is None and (episodic_life or max_episode_steps is not None or fused_games):
         raise ValueError('episodic_life, max_episode_steps and fused_games need a device game (game=)')
+    check_run_state_args(run_state, checkpoint_every, env_fns)
     if game is not None:
         multi_env = MultiEnv(create_game_environments(game, num_envs, seed=seed, full_action_set=mask_actions,
                                                       episodic_life=episodic_life,
@@ -90,9 +98,11 @@ def train_a2c_acktr(acktr, env_id, num_envs, num_steps, checkpoint_path, model_n
 
     with Session() as session:
         if checkpoint_path is not None:
-            load_model(checkpoint_path, model, optimizer, global_step, objective)
+            if load_model(checkpoint_path, model, optimizer, global_step, objective) and run_state:
+                load_run_state(checkpoint_path, model_name, global_step.value, agent, objective)
         step = global_step.value
         updates = 0
+        saved_step = None
         try:
             while step < max_step and (max_updates is None or updates < max_updates):
                 observations, actions, rewards, terminals, next_observations, infos = agent.interact(session)
@@ -122,11 +132,15 @@ def train_a2c_acktr(acktr, env_id, num_envs, num_steps, checkpoint_path, model_n
                                        **episode_rewards_by_game(multi_env.batched, episode_rewards))
                 if on_update is not None:
                     on_update(updates, model)
-                if checkpoint_path is not None and step % 100 == 0 and step > 0 and parallel.rank() == 0:
-                    save_model(checkpoint_path, model_name, step, model, optimizer, objective)
+                if checkpoint_path is not None and step % checkpoint_every == 0 and step > 0:
+                    save_checkpoint(checkpoint_path, model_name, step, model, optimizer, objective,
+                                    agent if run_state else None)
+                    saved_step = step
+            if run_state and checkpoint_path is not None and updates > 0 and saved_step != step:
+                save_checkpoint(checkpoint_path, model_name, step, model, optimizer, objective, agent)
         except KeyboardInterrupt:
             print('Stop requested')
-            if checkpoint_path is not None and parallel.rank() == 0:
+            if checkpoint_path is not None and parallel.rank() == 0 and not run_state:
                 save_model(checkpoint_path, model_name, step, model, optimizer, objective)
         finally:
             multi_env.close()
@@ -225,6 +239,35 @@ def save_model(checkpoint_path, model_name, step, model, optimizer, objective=No
     print('Saved model (step {})'.format(step))
 
 
+def check_run_state_args(run_state, checkpoint_every, env_fns):
+    if int(checkpoint_every) < 1:
+        raise ValueError('checkpoint_every must be at least 1, got {}'.format(checkpoint_every))
+    if run_state and env_fns is not None:
+        raise ValueError('run_state needs device envs: host-stepped envs keep their state in the host envs')
+
+
+def save_checkpoint(checkpoint_path, model_name, step, model, optimizer, objective=None, agent=None):
+    """Rank 0 writes the model checkpoint; with ``agent`` (``run_state=True``) every rank first writes its run
+    state, so the index never names a step whose rank-0 run state is missing."""
+    if agent is not None:
+        checkpoint.save_run_state(os.path.join(checkpoint_path, model_name), step, agent, objective)
+    if parallel.rank() == 0:
+        save_model(checkpoint_path, model_name, step, model, optimizer, objective)
+
+
+def load_run_state(checkpoint_path, model_name, step, agent, objective=None):
+    """This rank's run state of the model checkpoint just loaded (``step``: its global step)."""
+    path = checkpoint.run_state_path(os.path.join(checkpoint_path, model_name), step, parallel.rank())
+    if not os.path.exists(path):
+        raise ValueError('run_state=True, but the checkpoint of step {} has no run state for rank {} ({}); '
+                         'resume without run_state to restart the envs'.format(step, parallel.rank(), path))
+    blob = checkpoint.load_run_state(path, agent, objective)
+    if int(blob['global_step']) != int(step):
+        raise ValueError('{} was saved at step {}, the model checkpoint at {}'.format(path, int(blob['global_step']),
+                                                                                    step))
+    print('Loaded run state')
+
+
 if __name__ == '__main__':
     acktr = True
     argv = sys.argv[1:]
@@ -241,4 +284,7 @@ if __name__ == '__main__':
                     mask_actions='--mask-actions' in argv, game=game, episodic_life='--episodic-life' in argv,
                     max_episode_steps=(int(argv[argv.index('--max-episode-steps') + 1])
                                        if '--max-episode-steps' in argv else None),
-                    normalize_returns='--normalize-returns' in argv, fused_games='--fused-games' in argv)
+                    normalize_returns='--normalize-returns' in argv, fused_games='--fused-games' in argv,
+                    run_state='--run-state' in argv,
+                    checkpoint_every=(int(argv[argv.index('--checkpoint-every') + 1])
+                                      if '--checkpoint-every' in argv else 100))

@@ -19,10 +19,10 @@ import actorcritic.envs.atari.wrappers as wrappers
 from actorcritic import checkpoint, parallel
 from actorcritic.agents import MultiEnvAgent
 from actorcritic.envs.atari.model import AtariModel
-from actorcritic.examples.atari.a2c_acktr import (create_environments, create_game_environments,
-                                                  episode_rewards_by_game,
-                                                   create_host_environments, load_model, make_normalizer,
-                                                   save_model)
+from actorcritic.examples.atari.a2c_acktr import (check_run_state_args, create_environments,
+                                                  create_game_environments, create_host_environments,
+                                                  episode_rewards_by_game, load_model, load_run_state,
+                                                  make_normalizer, save_checkpoint, save_model)
 from actorcritic.multi_env import MultiEnv
 from actorcritic.nn import AdamOptimizer, ClipGlobalNormOptimizer, linear_decay
 from actorcritic.objectives import PPOObjective
@@ -32,7 +32,8 @@ from actorcritic.session import Session, get_or_create_global_step, no_op
 def train_ppo(env_id, num_envs, num_steps, checkpoint_path, model_name, summary_path=None, max_updates=None, seed=0,
               log_every=10, num_epochs=4, num_minibatches=4, clip_range=0.1, value_clip_range=None,
               minibatch='envs', env_fns=None, mask_actions=False, game=None, on_update=None, episodic_life=False,
-              max_episode_steps=None, normalize_returns=False, fused_games=False):
+              max_episode_steps=None, normalize_returns=False, fused_games=False, run_state=False,
+              checkpoint_every=100):
     """Trains an Atari model (conv3 64) with PPO.
 
     ``num_envs`` is per GPU; with WORLD_SIZE > 1 (torchrun) every rank steps its own shard.
@@ -46,12 +47,14 @@ def train_ppo(env_id, num_envs, num_steps, checkpoint_path, model_name, summary_
     ``mask_actions`` (``--mask-actions``): invalid-action masking, as in a2c_acktr.train_a2c_acktr.
     ``game`` (``--game catch|breakout``, or a mixed batch: ``catch+breakout``), ``episodic_life``
     (``--episodic-life``), ``max_episode_steps`` (``--max-episode-steps N``), ``checkpoint_path`` None and
-    ``on_update``, ``normalize_returns`` (``--normalize-returns``) and ``fused_games`` (``--fused-games``): as in
+    ``on_update``, ``normalize_returns`` (``--normalize-returns``), ``fused_games`` (``--fused-games``),
+    ``run_state`` (``--run-state``) and ``checkpoint_every`` (``--checkpoint-every K``): as in
     a2c_acktr.train_a2c_acktr.
     """
     parallel.init_from_env()
     if game is None and (episodic_life or max_episode_steps is not None or fused_games):
         raise ValueError('episodic_life, max_episode_steps and fused_games need a device game (game=)')
+    check_run_state_args(run_state, checkpoint_every, env_fns)
     if game is not None:
         multi_env = MultiEnv(create_game_environments(game, num_envs, seed=seed, full_action_set=mask_actions,
                                                       episodic_life=episodic_life,
@@ -84,9 +87,11 @@ def train_ppo(env_id, num_envs, num_steps, checkpoint_path, model_name, summary_
 
     with Session() as session:
         if checkpoint_path is not None:
-            load_model(checkpoint_path, model, optimizer, global_step, objective)
+            if load_model(checkpoint_path, model, optimizer, global_step, objective) and run_state:
+                load_run_state(checkpoint_path, model_name, global_step.value, agent, objective)
         step = global_step.value
         updates = 0
+        saved_step = None
         try:
             while step < max_step and (max_updates is None or updates < max_updates):
                 observations, actions, rewards, terminals, next_observations, infos = agent.interact(session)
@@ -118,11 +123,15 @@ def train_ppo(env_id, num_envs, num_steps, checkpoint_path, model_name, summary_
                                        **episode_rewards_by_game(multi_env.batched, episode_rewards))
                 if on_update is not None:
                     on_update(updates, model)
-                if checkpoint_path is not None and step % 100 == 0 and step > 0 and parallel.rank() == 0:
-                    save_model(checkpoint_path, model_name, step, model, optimizer, objective)
+                if checkpoint_path is not None and step % checkpoint_every == 0 and step > 0:
+                    save_checkpoint(checkpoint_path, model_name, step, model, optimizer, objective,
+                                    agent if run_state else None)
+                    saved_step = step
+            if run_state and checkpoint_path is not None and updates > 0 and saved_step != step:
+                save_checkpoint(checkpoint_path, model_name, step, model, optimizer, objective, agent)
         except KeyboardInterrupt:
             print('Stop requested')
-            if checkpoint_path is not None and parallel.rank() == 0:
+            if checkpoint_path is not None and parallel.rank() == 0 and not run_state:
                 save_model(checkpoint_path, model_name, step, model, optimizer, objective)
         finally:
             multi_env.close()
@@ -152,4 +161,7 @@ if __name__ == '__main__':
               mask_actions='--mask-actions' in argv, game=game, episodic_life='--episodic-life' in argv,
               max_episode_steps=(int(argv[argv.index('--max-episode-steps') + 1])
                                  if '--max-episode-steps' in argv else None),
-              normalize_returns='--normalize-returns' in argv, fused_games='--fused-games' in argv)
+              normalize_returns='--normalize-returns' in argv, fused_games='--fused-games' in argv,
+              run_state='--run-state' in argv,
+              checkpoint_every=(int(argv[argv.index('--checkpoint-every') + 1])
+                                if '--checkpoint-every' in argv else 100))

@@ -149,10 +149,12 @@ class ReturnNormalizer(object):
     of the last call) and ``bad_envs`` (int32 [1]) live on the host until the first use on a
     device (``to``), then on the engine's.  ``frozen`` (default False): the current stats are
     applied, neither ``stats`` nor ``carry`` changes (evaluation, or a fixed scale).
-    ``state_dict`` holds the stats and the settings, not ``carry``: env state is not
-    checkpointed either, so ``load_state_dict`` zeroes it.  Loading also REPLACES ``epsilon`` and
-    ``clip`` by the saved values (the statistics were applied with them); set them again after
-    loading to change them.
+    ``state_dict`` holds the stats and the settings, not ``carry``: that is per-env state of one
+    rank and travels with the run state (``carry_state`` / ``load_carry``;
+    checkpoint.save_run_state), so ``load_state_dict`` zeroes it.  The order of a resume is
+    therefore the model checkpoint first (``load_state_dict``), the run state second
+    (``load_carry``).  Loading also REPLACES ``epsilon`` and ``clip`` by the saved values (the
+    statistics were applied with them); set them again after loading to change them.
     """
 
     def __init__(self, groups, num_groups=None, group_names=None, epsilon=1e-8, clip=10.0):
@@ -226,6 +228,20 @@ class ReturnNormalizer(object):
     def state_dict(self):
         return {'stats': self.stats.detach().cpu().clone(), 'num_groups': self.num_groups, 'epsilon': self.epsilon,
                 'clip': self.clip, 'group_names': None if self.group_names is None else list(self.group_names)}
+
+    def carry_state(self):
+        """The envs' running discounted returns, a [N] f32 CPU tensor (a copy): the part of the
+        state that ``state_dict`` leaves out (class docstring)."""
+        return self.carry.detach().cpu().clone()
+
+    def load_carry(self, carry):
+        """Puts back what ``carry_state`` returned; call it AFTER ``load_state_dict`` (or
+        checkpoint.load), which zeroes the carry.  ValueError unless it is [num_envs] float32."""
+        t = torch.as_tensor(carry)
+        if tuple(t.shape) != (self.num_envs,) or t.dtype != torch.float32:
+            raise ValueError('carry of shape {} {} for a normalizer of {} envs (float32 [{}])'.format(
+                tuple(t.shape), t.dtype, self.num_envs, self.num_envs))
+        self.carry.copy_(t.to(self.device))
 
     def load_state_dict(self, state):
         stats = torch.as_tensor(state['stats'], dtype=torch.float64)

@@ -20,6 +20,13 @@ overwritten in place with the evaluation batch's and put back, so --eval-envs mu
 
 --normalize-returns trains with the rewards scaled by the running std of the discounted return,
 per game (actorcritic.return_norm); every line of a point then holds "inv", the scale per game.
+
+--checkpoint-dir DIR keeps checkpoints (every --checkpoint-every updates, default --every, and at the
+end) under DIR/seed<seed>, and a later call with the same arguments goes on from the newest one up to
+--updates.  With --run-state every checkpoint carries the run state and the continuation
+is the run it would have been, bit for bit: "updates", "env_steps" and the evaluation schedule follow
+the checkpoint's global step, so a curve cut at a lease boundary and resumed is the uncut curve
+("wall_s" alone restarts).  Without --run-state the weights resume and the envs start afresh.
 """
 import argparse
 import json
@@ -51,6 +58,17 @@ def run(args, seed, emit):
     episodes = lambda g: args.breakout_episodes if (mixed and g == 'breakout') else E
     rules = dict(episodic_life=args.episodic_life, max_episode_steps=args.max_episode_steps)
     fused = dict(fused_games=args.fused_games)
+    ckpt_dir, start = None, 0
+    if args.checkpoint_dir:
+        from actorcritic import checkpoint
+        ckpt_dir = os.path.join(args.checkpoint_dir, 'seed{}'.format(seed))
+        os.makedirs(ckpt_dir, exist_ok=True)
+        newest = checkpoint.latest(ckpt_dir)
+        if newest is not None:  # the curve goes on at that checkpoint's global step (one per update)
+            start = int(torch.load(newest, map_location='cpu', weights_only=True)['global_step'])
+    if start >= args.updates:
+        return
+    keep = dict(run_state=args.run_state, checkpoint_every=args.checkpoint_every or args.every)
 
     def stats(returns):
         r = returns.double().flatten()
@@ -59,7 +77,7 @@ def run(args, seed, emit):
     eval_envs = lambda g: DeviceGameEnvs(g, args.eval_envs, num_actions=num_actions, seed=1000 + seed,
                                          max_episode_steps=args.max_episode_steps)
     tag = lambda g: dict(eval_game=g) if mixed else {}
-    for g in eval_games:
+    for g in eval_games if start == 0 else ():  # (a resumed curve has its first lines already)
         emit(dict(head, policy='uniform', updates=0, env_steps=0, **tag(g),
                   **stats(evaluate(None, eval_envs(g), episodes(g), uniform=True, seed=seed))))
     norm = False
@@ -82,6 +100,7 @@ def run(args, seed, emit):
             words.copy_(saved)
 
     def on_update(updates, model):
+        updates += start  # (of the whole run: the example counts this call's)
         if updates % args.every == 0 or updates == args.updates:
             torch.cuda.synchronize()
             train_s = time.perf_counter() - t0
@@ -93,12 +112,13 @@ def run(args, seed, emit):
                           **stats(play(model, g))))
 
     if args.algo == 'ppo':
-        train_ppo(args.game, N, T, None, args.game, max_updates=args.updates, seed=seed, game=args.game,
-                  on_update=on_update, mask_actions=args.mask_actions, normalize_returns=norm, **rules, **fused)
+        train_ppo(args.game, N, T, ckpt_dir, args.game, max_updates=args.updates - start, seed=seed, game=args.game,
+                  on_update=on_update, mask_actions=args.mask_actions, normalize_returns=norm, **rules, **fused,
+                  **keep)
     else:
-        train_a2c_acktr(args.algo == 'acktr', args.game, N, T, None, args.game, max_updates=args.updates, seed=seed,
-                        game=args.game, on_update=on_update, mask_actions=args.mask_actions,
-                        normalize_returns=norm, **rules, **fused)
+        train_a2c_acktr(args.algo == 'acktr', args.game, N, T, ckpt_dir, args.game, max_updates=args.updates - start,
+                        seed=seed, game=args.game, on_update=on_update, mask_actions=args.mask_actions,
+                        normalize_returns=norm, **rules, **fused, **keep)
 
 
 def main():
@@ -122,10 +142,17 @@ def main():
                     help='scale rewards by the running std of the discounted return, per game')
     ap.add_argument('--fused-games', action='store_true',
                     help='train through the rollout\'s fused step (DeviceGameEnvs(fused_step=True))')
+    ap.add_argument('--checkpoint-dir', default=None,
+                    help='keep checkpoints under DIR/seed<seed> and go on from the newest one')
+    ap.add_argument('--checkpoint-every', type=int, default=None, help='updates between checkpoints (default: --every)')
+    ap.add_argument('--run-state', action='store_true',
+                    help='checkpoints carry the run state: the resumed run is the uncut one, bit for bit')
     ap.add_argument('--out', default=None, help='also append the JSON lines to this file')
     args = ap.parse_args()
     if args.mask_actions and args.eval_envs != args.envs:
         ap.error('--mask-actions needs --eval-envs equal to --envs (one mask word per env)')
+    if args.run_state and not args.checkpoint_dir:
+        ap.error('--run-state needs --checkpoint-dir')
     if args.steps is None:
         args.steps = {'a2c': 5, 'acktr': 20, 'ppo': 128}[args.algo]  # the examples' rollout lengths
     out = open(args.out, 'a') if args.out else None
