@@ -132,6 +132,9 @@ _SIGS = {
     'acmi_retnorm_scan': (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_float, c_vp, c_vp, c_vp, c_vp, c_vp]),
     'acmi_retnorm_apply': (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_vp, c_vp, ctypes.c_double, c_float, c_vp,
                                    c_vp, c_vp]),
+    # episode statistics per group: (episode rewards, groups, N, T, G, length carry, ws, acc, bad_envs nullable)
+    'acmi_epstats_ws_doubles': (c_i64, [c_i64]),
+    'acmi_epstats_update': (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp]),
     'acmi_a2c_loss_ws_floats': (c_i64, [c_int]),
     'acmi_a2c_loss': (c_int, [c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_float, c_float, c_float,
                               c_vp, c_int, c_vp, c_vp, c_vp]),

@@ -124,12 +124,17 @@ class _HostRolloutBuffers(object):
 class MultiEnvAgent(Agent):
     """Multiple envs (MultiEnv), multiple steps (agents.py:134-228)."""
 
-    def __init__(self, multi_env, model, num_steps, copy_batches=False, mask_actions=False):
+    def __init__(self, multi_env, model, num_steps, copy_batches=False, mask_actions=False, episode_stats=None):
         """mask_actions: take the batched env's ``legal_action_masks`` (one word per env)
         and set them on the model (AtariModel.set_action_masks): every action is then
         drawn from its env's legal set, and the losses / K-FAC statistics of that model
         run over it.  Off by default.  (Every rollout form follows the masks the model
-        holds, however they were set.)"""
+        holds, however they were set.)
+        episode_stats: an episode_stats.EpisodeStats, or True for ``EpisodeStats.for_envs(multi_env)``:
+        after every complete rollout the agent adds the rollout's episode rewards to it (device
+        paths: two launches on the engine's stream, no host wait; the list path: on the host);
+        ``agent.episode_stats`` is the object, its state part of ``run_state()``.  None (default):
+        nothing is allocated and the rollout runs as it always did."""
         self._env = multi_env
         self._model = model
         self._num_steps = num_steps
@@ -140,6 +145,15 @@ class MultiEnvAgent(Agent):
         # the last rollout's truncations, [N, T] bool on the device (the feed of
         # model.truncations_placeholder); None for envs that emit none
         self.last_truncations = None
+        self.episode_stats = None
+        if episode_stats is not None and episode_stats is not False:
+            from actorcritic.episode_stats import EpisodeStats
+            self.episode_stats = EpisodeStats.for_envs(multi_env) if episode_stats is True else episode_stats
+            if not isinstance(self.episode_stats, EpisodeStats):
+                raise TypeError('episode_stats: an EpisodeStats or True, got {}'.format(type(episode_stats).__name__))
+            if self.episode_stats.num_envs != multi_env.num_envs:
+                raise ValueError('episode_stats of {} envs for an agent of {}'.format(self.episode_stats.num_envs,
+                                                                                   multi_env.num_envs))
         if self._mask_actions:
             masks = getattr(getattr(multi_env, 'batched', None), 'legal_action_masks', None)
             if masks is None:
@@ -179,8 +193,12 @@ class MultiEnvAgent(Agent):
             terminal_steps.append(terminals)
             info_steps.append(infos)
         self._observations = next_observations
+        infos = transpose_list(info_steps)
+        if self.episode_stats is not None:
+            from actorcritic.envs.atari.wrappers import EpisodeInfoWrapper
+            self.episode_stats.update(EpisodeInfoWrapper.get_episode_rewards_from_info_batch(infos))
         return (transpose_list(observation_steps), transpose_list(action_steps), transpose_list(reward_steps),
-                transpose_list(terminal_steps), next_observations, transpose_list(info_steps))
+                transpose_list(terminal_steps), next_observations, infos)
 
     # -- device rollout ------------------------------------------------------------
     def _rollout_halves(self, eng, env, rb, N, T, A, seed, dev_ctr=False):
@@ -328,7 +346,8 @@ class MultiEnvAgent(Agent):
     def run_state(self):
         """What the next ``interact()`` reads beside the model, between two complete rollouts:
         ``{'next_obs': [N,84,84,4] u8, 'sample_counter': int, 'env': the batched env's
-        state_dict()}``, CPU tensors and plain ints.  Waits for the engine's stream (and the
+        state_dict()}`` and, with episode statistics, ``'episode_stats'``: their ``state_dict()``;
+        CPU tensors and plain ints.  Waits for the engine's stream (and the
         side stream of the two-halves form).  ValueError before the first ``interact()`` and
         for host-stepped or list-path envs.  The rollout length is not part of it."""
         env = self._stateful_env()
@@ -339,15 +358,22 @@ class MultiEnvAgent(Agent):
         torch.cuda.current_stream(eng.device).synchronize()
         if rb.side is not None:
             rb.side.synchronize()
-        return {'next_obs': rb.next_obs.detach().cpu().clone(), 'sample_counter': int(eng.sample_counter),
-                'env': env.state_dict()}
+        state = {'next_obs': rb.next_obs.detach().cpu().clone(), 'sample_counter': int(eng.sample_counter),
+                 'env': env.state_dict()}
+        if self.episode_stats is not None:  # (the interval's accumulators and the running episodes' lengths)
+            state['episode_stats'] = self.episode_stats.state_dict()
+        return state
 
     def load_run_state(self, state):
         """Continues from a ``run_state()``: fills ``next_obs`` (making the rollout buffers for
         (N, this agent's T) if need be) and marks the envs as reset, so that no ``reset_into``
         follows; sets the engine's ``sample_counter``; loads the env state (ValueError when the
-        envs are not the saved ones).  Load the model checkpoint first (checkpoint.load)."""
+        envs are not the saved ones); with episode statistics, loads ``state['episode_stats']``
+        (ValueError when it is missing or of other groups).  Load the model checkpoint first
+        (checkpoint.load)."""
         env = self._stateful_env()
+        if self.episode_stats is not None and 'episode_stats' not in state:
+            raise ValueError('run state: no episode_stats for the agent\'s EpisodeStats')
         eng = self._model.engine
         N, T = env.num_envs, self._num_steps
         nxt = state['next_obs']
@@ -359,12 +385,16 @@ class MultiEnvAgent(Agent):
         self._bufs.next_obs.copy_(nxt.to(eng.device))
         self._observations = self._bufs.next_obs
         eng.sample_counter = int(state['sample_counter'])
+        if self.episode_stats is not None:
+            self.episode_stats.load_state_dict(state['episode_stats'])
 
     def _batch(self, eng, rb, N, T):
         """interact()'s 6-tuple from the rollout buffers, registered for the update."""
         from actorcritic.envs.atari.model import ForwardOut
         from actorcritic.envs.atari.wrappers import EpisodeInfoBatch
         self._observations = rb.next_obs
+        if self.episode_stats is not None:  # (after everything the rollout joined on this stream)
+            self.episode_stats.update(rb.episode_rewards, eng.stream())
         out = (rb.obs, rb.actions, rb.rewards, rb.terminals.view(torch.bool), rb.next_obs, rb.episode_rewards)
         trunc = rb.truncations.view(torch.bool) if rb.emits_truncations else None
         if self._copy:

@@ -9,8 +9,8 @@ policy_entropy, episode_reward).
 
 Beside a model checkpoint every rank may write its RUN STATE, ``<prefix>-<step>.run<rank>.pt``
 (``save_run_state`` / ``load_run_state``): the envs' state, the next observations, the sample
-counter and the return normaliser's carry -- with it a run on the device envs resumes bit for
-bit.  The model checkpoint and the index file are what they were without it.
+counter, the return normaliser's carry and the agent's episode statistics -- with
+it a run on the device envs resumes bit for bit.  The model checkpoint and the index file are what they were without it.
 """
 
 import json
@@ -126,8 +126,9 @@ def run_state_path(prefix, step, rank):
 
 def save_run_state(prefix, step, agent, objective=None):
     """Called by EVERY rank, between an update and the next ``interact()``: writes this rank's
-    ``agent.run_state()`` (next observations, sample counter, env state) and, with a
-    ReturnNormalizer on ``objective``, its ``carry`` to ``run_state_path(prefix, step, rank)``.
+    ``agent.run_state()`` (next observations, sample counter, env state and, for an agent with
+    episode statistics, their ``episode_stats`` state) and, with a ReturnNormalizer on
+    ``objective``, its ``carry`` to ``run_state_path(prefix, step, rank)``.
     Tensors, ints and dicts of them only (``torch.load(weights_only=True)``); ``format``,
     ``rank``, ``world_size`` and ``global_step`` say what the file is.  Neither the model
     checkpoint nor the ``checkpoint`` index is touched."""
@@ -149,7 +150,8 @@ def load_run_state(path, agent, objective=None):
     """Continues ``agent`` (and ``objective``'s ReturnNormalizer) from a ``save_run_state`` file.
     Call it AFTER ``load``: loading a model checkpoint zeroes the normalizer's carry.  ValueError
     when the file is another rank's or another world size's (the env shards would differ), of
-    another format, or lacks the carry a normalizer needs; and whatever
+    another format, or lacks the carry a normalizer needs or the ``episode_stats`` an agent with
+    episode statistics needs (a file that has them loads into an agent without); and whatever
     ``agent.load_run_state`` refuses.  -> the blob (``global_step``: the step it was saved at)."""
     from actorcritic import parallel
     blob = torch.load(path, map_location='cpu', weights_only=True)
@@ -165,7 +167,12 @@ def load_run_state(path, agent, objective=None):
     norm = _normalizer(objective)
     if norm is not None and 'retnorm/carry' not in blob:
         raise ValueError('{}: no retnorm/carry for the objective\'s ReturnNormalizer'.format(path))
-    agent.load_run_state({k: blob[k] for k in ('next_obs', 'sample_counter', 'env')})
+    keys = ('next_obs', 'sample_counter', 'env')
+    if getattr(agent, 'episode_stats', None) is not None:
+        if 'episode_stats' not in blob:
+            raise ValueError('{}: no episode_stats for the agent\'s EpisodeStats'.format(path))
+        keys += ('episode_stats',)
+    agent.load_run_state({k: blob[k] for k in keys})
     if norm is not None:
         norm.load_carry(blob['retnorm/carry'])
     return blob

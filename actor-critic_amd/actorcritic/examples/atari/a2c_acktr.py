@@ -26,7 +26,7 @@ from actorcritic.session import Session, get_or_create_global_step, no_op
 def train_a2c_acktr(acktr, env_id, num_envs, num_steps, checkpoint_path, model_name, summary_path=None,
                     max_updates=None, seed=0, log_every=10, env_fns=None, mask_actions=False, game=None,
                     on_update=None, episodic_life=False, max_episode_steps=None, normalize_returns=False,
-                    fused_games=False, run_state=False, checkpoint_every=100):
+                    fused_games=False, run_state=False, checkpoint_every=100, episode_stats=False):
     """Trains an Atari model with A2C (RMSProp, conv3 64) or ACKTR (K-FAC, conv3 32).
 
     ``num_envs`` is per GPU; with WORLD_SIZE > 1 (torchrun) every rank steps its own shard.
@@ -60,6 +60,16 @@ def train_a2c_acktr(acktr, env_id, num_envs, num_steps, checkpoint_path, model_n
     step; at start the latest model checkpoint is loaded WITH this rank's run state (a missing file is a
     ValueError, not a silent reset), and the run continues bit for bit.  A stop request then writes nothing:
     it may fall between a rollout and its update, and the last pair stays the point to resume from.
+    ``episode_stats`` (``--episode-stats``): the agent keeps episode statistics on the device
+    (actorcritic.episode_stats: returns AND lengths of every episode that ended since the last log line, per
+    game, over all ranks; an EpisodeStats of the caller's own is taken as it is).  The loop then never copies
+    ``infos`` to the host; with a ``summary_path`` (given to every rank), on the updates that log every rank
+    calls ``read()`` (a collective) and rank 0 logs ``episode_reward`` (now the interval's mean),
+    ``episode_reward_std`` / ``_min`` / ``_max``, ``episode_length``, ``episode_length_max`` and ``episodes``,
+    per game too (``/<game>``) when the batch holds more than one.  With ``run_state`` the statistics travel
+    with the run state.  Without a ``summary_path`` the loop never reads: the statistics gather until the
+    caller does (scripts/learn_games.py reads them at its evaluation points).  Off (default):
+    ``episode_reward`` is the last rollout's mean on rank 0, as ever.
     """
     parallel.init_from_env()
     if game is None and (episodic_life or max_episode_steps is not None or fused_games):
@@ -77,7 +87,10 @@ def train_a2c_acktr(acktr, env_id, num_envs, num_steps, checkpoint_path, model_n
 
     conv3_num_filters = 32 if acktr else 64
     model = AtariModel(multi_env.observation_space, multi_env.action_space, conv3_num_filters, random_seed=seed)
-    agent = MultiEnvAgent(multi_env, model, num_steps, mask_actions=mask_actions)
+    agent = MultiEnvAgent(multi_env, model, num_steps, mask_actions=mask_actions,
+                          episode_stats=episode_stats or None)
+    stats = agent.episode_stats
+    read_stats = stats is not None and bool(summary_path)  # (every rank knows the path; rank 0 alone writes)
     normalizer = make_normalizer(normalize_returns, multi_env)
     objective = A2CObjective(model, discount_factor=0.99, entropy_regularization_strength=0.01,
                              normalize_returns=normalizer)
@@ -107,10 +120,11 @@ def train_a2c_acktr(acktr, env_id, num_envs, num_steps, checkpoint_path, model_n
             while step < max_step and (max_updates is None or updates < max_updates):
                 observations, actions, rewards, terminals, next_observations, infos = agent.interact(session)
                 episode_rewards = wrappers.EpisodeInfoWrapper.get_episode_rewards_from_info_batch(infos) \
-                    if summary_writer is not None else None
+                    if summary_writer is not None and stats is None else None
+                log_now = step % log_every == 0
 
                 fetches = [summary_op, global_step, optimize_op]
-                if summary_writer is not None and step % log_every == 0:
+                if summary_writer is not None and log_now:
                     fetches += [objective.policy_loss, objective.baseline_loss, objective.mean_entropy]
                 feed_dict = {
                     model.observations_placeholder: observations,
@@ -124,12 +138,13 @@ def train_a2c_acktr(acktr, env_id, num_envs, num_steps, checkpoint_path, model_n
                 out = session.run(fetches, feed_dict=feed_dict, host=len(fetches) > 3)
                 step = global_step.value
                 updates += 1
+                # episode statistics: the interval's, over all ranks -- a collective, so EVERY rank reads
+                interval = stats.read() if read_stats and log_now else None
                 if len(out) > 3:
-                    mean_episode_reward = (np.nan if np.all(np.isnan(episode_rewards))
-                                           else float(np.nanmean(episode_rewards)))
+                    episode_scalars = stats.log_scalars(interval) if read_stats else \
+                        episode_reward_scalars(multi_env.batched, episode_rewards)
                     summary_writer.add(step, policy_loss=float(out[3]), baseline_loss=float(out[4]),
-                                       policy_entropy=float(out[5]), episode_reward=mean_episode_reward,
-                                       **episode_rewards_by_game(multi_env.batched, episode_rewards))
+                                       policy_entropy=float(out[5]), **episode_scalars)
                 if on_update is not None:
                     on_update(updates, model)
                 if checkpoint_path is not None and step % checkpoint_every == 0 and step > 0:
@@ -182,6 +197,13 @@ def create_game_environments(game, num_envs, seed=0, full_action_set=False, epis
     return DeviceGameEnvs(game, num_envs, num_actions=18 if full_action_set else None, seed=seed,
                           env_offset=env_offset, episodic_life=episodic_life, max_episode_steps=max_episode_steps,
                           fused_step=fused_step)
+
+
+def episode_reward_scalars(batched, episode_rewards):
+    """The scalar log's ``episode_reward`` of one rollout's [N][T] episode rewards (the reference's: their
+    nanmean, NaN when no episode ended), and the per-game keys of a mixed batch."""
+    mean_episode_reward = (np.nan if np.all(np.isnan(episode_rewards)) else float(np.nanmean(episode_rewards)))
+    return dict(episode_reward=mean_episode_reward, **episode_rewards_by_game(batched, episode_rewards))
 
 
 def episode_rewards_by_game(batched, episode_rewards):
@@ -285,6 +307,6 @@ if __name__ == '__main__':
                     max_episode_steps=(int(argv[argv.index('--max-episode-steps') + 1])
                                        if '--max-episode-steps' in argv else None),
                     normalize_returns='--normalize-returns' in argv, fused_games='--fused-games' in argv,
-                    run_state='--run-state' in argv,
+                    run_state='--run-state' in argv, episode_stats='--episode-stats' in argv,
                     checkpoint_every=(int(argv[argv.index('--checkpoint-every') + 1])
                                       if '--checkpoint-every' in argv else 100))

@@ -13,15 +13,13 @@ all env-steps of the batch per epoch (objectives.PPOOptimizeOp).
 import os
 import sys
 
-import numpy as np
-
 import actorcritic.envs.atari.wrappers as wrappers
 from actorcritic import checkpoint, parallel
 from actorcritic.agents import MultiEnvAgent
 from actorcritic.envs.atari.model import AtariModel
 from actorcritic.examples.atari.a2c_acktr import (check_run_state_args, create_environments,
                                                   create_game_environments, create_host_environments,
-                                                  episode_rewards_by_game, load_model, load_run_state,
+                                                  episode_reward_scalars, load_model, load_run_state,
                                                   make_normalizer, save_checkpoint, save_model)
 from actorcritic.multi_env import MultiEnv
 from actorcritic.nn import AdamOptimizer, ClipGlobalNormOptimizer, linear_decay
@@ -33,7 +31,7 @@ def train_ppo(env_id, num_envs, num_steps, checkpoint_path, model_name, summary_
               log_every=10, num_epochs=4, num_minibatches=4, clip_range=0.1, value_clip_range=None,
               minibatch='envs', env_fns=None, mask_actions=False, game=None, on_update=None, episodic_life=False,
               max_episode_steps=None, normalize_returns=False, fused_games=False, run_state=False,
-              checkpoint_every=100):
+              checkpoint_every=100, episode_stats=False):
     """Trains an Atari model (conv3 64) with PPO.
 
     ``num_envs`` is per GPU; with WORLD_SIZE > 1 (torchrun) every rank steps its own shard.
@@ -48,8 +46,8 @@ def train_ppo(env_id, num_envs, num_steps, checkpoint_path, model_name, summary_
     ``game`` (``--game catch|breakout``, or a mixed batch: ``catch+breakout``), ``episodic_life``
     (``--episodic-life``), ``max_episode_steps`` (``--max-episode-steps N``), ``checkpoint_path`` None and
     ``on_update``, ``normalize_returns`` (``--normalize-returns``), ``fused_games`` (``--fused-games``),
-    ``run_state`` (``--run-state``) and ``checkpoint_every`` (``--checkpoint-every K``): as in
-    a2c_acktr.train_a2c_acktr.
+    ``run_state`` (``--run-state``), ``checkpoint_every`` (``--checkpoint-every K``) and ``episode_stats``
+    (``--episode-stats``): as in a2c_acktr.train_a2c_acktr.
     """
     parallel.init_from_env()
     if game is None and (episodic_life or max_episode_steps is not None or fused_games):
@@ -66,7 +64,10 @@ def train_ppo(env_id, num_envs, num_steps, checkpoint_path, model_name, summary_
         multi_env = MultiEnv(create_environments(env_id, num_envs, seed=seed, full_action_set=mask_actions))
 
     model = AtariModel(multi_env.observation_space, multi_env.action_space, 64, random_seed=seed)
-    agent = MultiEnvAgent(multi_env, model, num_steps, mask_actions=mask_actions)
+    agent = MultiEnvAgent(multi_env, model, num_steps, mask_actions=mask_actions,
+                          episode_stats=episode_stats or None)
+    stats = agent.episode_stats
+    read_stats = stats is not None and bool(summary_path)  # (every rank knows the path; rank 0 alone writes)
     normalizer = make_normalizer(normalize_returns, multi_env)
     objective = PPOObjective(model, discount_factor=0.99, entropy_regularization_strength=0.01,
                              clip_range=clip_range, value_clip_range=value_clip_range, gae_lambda=0.95,
@@ -96,10 +97,11 @@ def train_ppo(env_id, num_envs, num_steps, checkpoint_path, model_name, summary_
             while step < max_step and (max_updates is None or updates < max_updates):
                 observations, actions, rewards, terminals, next_observations, infos = agent.interact(session)
                 episode_rewards = wrappers.EpisodeInfoWrapper.get_episode_rewards_from_info_batch(infos) \
-                    if summary_writer is not None else None
+                    if summary_writer is not None and stats is None else None
+                log_now = step % log_every == 0
 
                 fetches = [summary_op, global_step, optimize_op]
-                if summary_writer is not None and step % log_every == 0:
+                if summary_writer is not None and log_now:
                     fetches += [objective.policy_loss, objective.baseline_loss, objective.mean_entropy,
                                 objective.approx_kl, objective.clip_fraction]
                 feed_dict = {
@@ -114,13 +116,14 @@ def train_ppo(env_id, num_envs, num_steps, checkpoint_path, model_name, summary_
                 out = session.run(fetches, feed_dict=feed_dict, host=len(fetches) > 3)
                 step = global_step.value
                 updates += 1
+                # episode statistics: the interval's, over all ranks -- a collective, so EVERY rank reads
+                interval = stats.read() if read_stats and log_now else None
                 if len(out) > 3:
-                    mean_episode_reward = (np.nan if np.all(np.isnan(episode_rewards))
-                                           else float(np.nanmean(episode_rewards)))
+                    episode_scalars = stats.log_scalars(interval) if read_stats else \
+                        episode_reward_scalars(multi_env.batched, episode_rewards)
                     summary_writer.add(step, policy_loss=float(out[3]), baseline_loss=float(out[4]),
                                        policy_entropy=float(out[5]), approx_kl=float(out[6]),
-                                       clip_fraction=float(out[7]), episode_reward=mean_episode_reward,
-                                       **episode_rewards_by_game(multi_env.batched, episode_rewards))
+                                       clip_fraction=float(out[7]), **episode_scalars)
                 if on_update is not None:
                     on_update(updates, model)
                 if checkpoint_path is not None and step % checkpoint_every == 0 and step > 0:
@@ -162,6 +165,6 @@ if __name__ == '__main__':
               max_episode_steps=(int(argv[argv.index('--max-episode-steps') + 1])
                                  if '--max-episode-steps' in argv else None),
               normalize_returns='--normalize-returns' in argv, fused_games='--fused-games' in argv,
-              run_state='--run-state' in argv,
+              run_state='--run-state' in argv, episode_stats='--episode-stats' in argv,
               checkpoint_every=(int(argv[argv.index('--checkpoint-every') + 1])
                                 if '--checkpoint-every' in argv else 100))

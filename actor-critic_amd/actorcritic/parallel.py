@@ -60,6 +60,13 @@ def allreduce_sum_(t, force=False):
     return t
 
 
+def allreduce_max_(t):
+    """In-place MAX over ranks (EpisodeStats.read: the maxima and the negated minima)."""
+    if world_size() > 1:
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+    return t
+
+
 def allreduce_sum_async(t):
     """Starts an in-place SUM all-reduce; the returned work's wait() makes the current
     stream wait for it (RCCL/NCCL runs collectives on its own stream)."""

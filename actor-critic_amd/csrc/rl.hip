@@ -224,16 +224,41 @@ __global__ void retnorm_scan_kernel(const float* r, const uint8_t* d, const uint
   if (groups[n] >= G && bad_envs != nullptr) atomicAdd(bad_envs, 1);
 }
 
+// The group reduction of the per-env partials part[n][NS + NM] (retnorm's moments, the
+// episode statistics below), one wave per group g: the lanes walk the envs lane-strided in
+// ascending order and take those of the group, then the butterfly.  Columns 0..NS-1 are
+// summed, columns NS.. are maximised (from -inf); every lane holds the result in v.
+// -> the number of envs of the group (exact).
+template <int NS, int NM>
+__device__ __forceinline__ double group_reduce(const double* part, const uint8_t* groups, int N, int g,
+                                               double (&v)[NS + NM]) {
+  constexpr int W = NS + NM;
+  double c = 0.0;
+#pragma unroll
+  for (int k = 0; k < W; ++k) v[k] = k < NS ? 0.0 : -INFINITY;
+  for (int n = threadIdx.x; n < N; n += 64) {
+    if (groups[n] == g) {
+      const double* p = part + (long long)W * n;
+      c += 1.0;
+#pragma unroll
+      for (int k = 0; k < NS; ++k) v[k] += p[k];
+#pragma unroll
+      for (int k = NS; k < W; ++k) v[k] = fmax(v[k], p[k]);
+    }
+  }
+  c = wave_sum_d(c);
+#pragma unroll
+  for (int k = 0; k < NS; ++k) v[k] = wave_sum_d(v[k]);
+#pragma unroll
+  for (int k = NS; k < W; ++k) v[k] = wave_max_d(v[k]);
+  return c;
+}
+
 __global__ void retnorm_groups_kernel(const double* part, const uint8_t* groups, int N, int T, double* moments) {
   const int g = blockIdx.x;  // one wave per group
-  double c = 0.0, s = 0.0, q = 0.0;
-  for (int n = threadIdx.x; n < N; n += 64) {
-    if (groups[n] == g) c += 1.0, s += part[2LL * n], q += part[2LL * n + 1];
-  }
-  c = wave_sum_d(c);  // (a count of envs: exact)
-  s = wave_sum_d(s);
-  q = wave_sum_d(q);
-  if (threadIdx.x == 0) moments[3 * g] = c * (double)T, moments[3 * g + 1] = s, moments[3 * g + 2] = q;
+  double v[2];
+  const double c = group_reduce<2, 0>(part, groups, N, g, v);
+  if (threadIdx.x == 0) moments[3 * g] = c * (double)T, moments[3 * g + 1] = v[0], moments[3 * g + 2] = v[1];
 }
 
 __global__ void __launch_bounds__(RETNORM_APPLY_BLOCK)
@@ -274,6 +299,61 @@ __global__ void __launch_bounds__(RETNORM_APPLY_BLOCK)
     out[i] = v;
     e += de, t += dt;
     if (t >= T) t -= T, ++e;
+  }
+}
+
+// ---------------------------------------------------------------------------
+// episode statistics per group (an option beyond the reference): returns and
+// lengths of the episodes that ended in a rollout, accumulated on the device.
+// acmi.h states the semantics.  Two launches a call, retnorm_scan's shape:
+//   epstats_scan_kernel    one thread per env: walks the env's T episode
+//                          rewards, counts its steps from length_carry[n], the
+//                          env's eight partials into ws[n][8]
+//   epstats_groups_kernel  one wave per group: group_reduce (sums 0..3, maxima
+//                          4..7), lane 0 merges into acc[g]
+// "No episode" is a NaN by its BITS: a comparison x != x is the optimiser's
+// to fold.
+// ---------------------------------------------------------------------------
+constexpr int EPSTATS_COLS = 8;
+
+__global__ void epstats_scan_kernel(const float* ep, const uint8_t* groups, int N, int T, int G,
+                                    int32_t* length_carry, double* part, int32_t* bad_envs) {
+  const int n = blockIdx.x * blockDim.x + threadIdx.x;
+  if (n >= N) return;
+  int len = length_carry[n];
+  double c = 0.0, s = 0.0, q = 0.0, sl = 0.0;
+  double rmax = -INFINITY, rmin = -INFINITY, lmax = -INFINITY, lmin = -INFINITY;  // (the minima negated)
+  for (int t = 0; t < T; ++t) {
+    const float x = ep[(long long)n * T + t];
+    ++len;
+    if ((__float_as_uint(x) & 0x7fffffffu) <= 0x7f800000u) {  // not a NaN: an episode ended here
+      const double r = x, l = len;
+      c += 1.0;
+      s += r;
+      q += r * r;  // (r*r is exact in double: a fused multiply-add rounds the same sum)
+      sl += l;
+      rmax = fmax(rmax, r), rmin = fmax(rmin, -r);
+      lmax = fmax(lmax, l), lmin = fmax(lmin, -l);
+      len = 0;
+    }
+  }
+  length_carry[n] = len;
+  double* p = part + (long long)EPSTATS_COLS * n;
+  p[0] = c, p[1] = s, p[2] = q, p[3] = sl;
+  p[4] = rmax, p[5] = rmin, p[6] = lmax, p[7] = lmin;
+  if (groups[n] >= G && bad_envs != nullptr) atomicAdd(bad_envs, 1);
+}
+
+__global__ void epstats_groups_kernel(const double* part, const uint8_t* groups, int N, double* acc) {
+  const int g = blockIdx.x;  // one wave per group
+  double v[EPSTATS_COLS];
+  group_reduce<4, 4>(part, groups, N, g, v);
+  if (threadIdx.x == 0) {
+    double* a = acc + EPSTATS_COLS * g;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) a[k] += v[k];
+#pragma unroll
+    for (int k = 4; k < EPSTATS_COLS; ++k) a[k] = fmax(a[k], v[k]);
   }
 }
 
@@ -840,6 +920,22 @@ int acmi_retnorm_apply(const float* rewards, const uint8_t* groups, int N, int T
   hipLaunchKernelGGL(retnorm_apply_kernel, dim3(1), dim3(RETNORM_APPLY_BLOCK), 0, (hipStream_t)stream, rewards,
                      groups, N, T, G, moments, stats, eps, clip, out, inv_out);
   ACMI_LAUNCH_CHECK("acmi_retnorm_apply");
+  return ACMI_OK;
+}
+
+int64_t acmi_epstats_ws_doubles(int64_t N) { return N < 1 ? 0 : EPSTATS_COLS * N; }
+
+int acmi_epstats_update(const float* episode_rewards, const uint8_t* groups, int N, int T, int G,
+                        int32_t* length_carry, double* ws, double* acc, int32_t* bad_envs, acmi_stream_t stream) {
+  ACMI_REQUIRE(episode_rewards && groups && length_carry && ws && acc, ACMI_ERR_ARG,
+               "acmi_epstats_update: a required pointer is NULL");
+  ACMI_REQUIRE(N >= 1 && T >= 1 && G >= 1 && G <= RETNORM_MAX_GROUPS, ACMI_ERR_ARG,
+               "acmi_epstats_update: N=%d, T=%d must be at least 1 and G=%d in 1..%d", N, T, G, RETNORM_MAX_GROUPS);
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(epstats_scan_kernel, dim3(cdiv(N, RETNORM_SCAN_BLOCK)), dim3(RETNORM_SCAN_BLOCK), 0, s,
+                     episode_rewards, groups, N, T, G, length_carry, ws, bad_envs);
+  hipLaunchKernelGGL(epstats_groups_kernel, dim3(G), dim3(64), 0, s, ws, groups, N, acc);
+  ACMI_LAUNCH_CHECK("acmi_epstats_update");
   return ACMI_OK;
 }
 

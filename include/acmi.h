@@ -337,6 +337,43 @@ int acmi_retnorm_apply(const float* rewards, const uint8_t* groups, int N, int T
                        const double* moments, double* stats, double eps, float clip,
                        float* out, float* inv_out, acmi_stream_t stream);
 
+/* Episode statistics per group of envs (per game), accumulated on the device:
+ * the return and the length of every episode that ended in a rollout; an
+ * option beyond the reference, which averages one batch's episode rewards on
+ * the host.  State across calls: length_carry[N] i32 (the steps of each env's
+ * running episode, starts 0), acc[G][8] f64, groups[N] u8; G in 1..64.  Per
+ * call, over episode_rewards[N][T] f32 (what the steppers write: an episode's
+ * total reward at the step that ended it, a NaN everywhere else):
+ *   scan    per env, ascending t: len += 1; if episode_rewards[n][t] is not a
+ *           NaN, (ret = that float, len) is one sample of group groups[n] and
+ *           len = 0; length_carry[n] = len at the end.  "Is a NaN" is decided
+ *           on the bits, (bits & 0x7fffffff) > 0x7f800000: every NaN payload
+ *           means "no episode", +-inf is a sample.
+ *   acc[g]  column 0: episodes, 1: sum ret, 2: sum ret^2, 3: sum len,
+ *           4: max ret, 5: max(-ret), 6: max len, 7: max(-len).  Columns 0-3
+ *           are sums in double (ret converted to double first), in a fixed
+ *           order without floating-point atomics: same bytes in, same bytes
+ *           out.  A cleared accumulator holds 0 in columns 0-3 and -inf in
+ *           columns 4-7; the negated minima let one MAX all-reduce serve both
+ *           ends.  (+0 and -0 compare equal: which of them a zero maximum
+ *           holds is not specified.)  ws: acmi_epstats_ws_doubles(N) doubles.
+ * A call ADDS its samples to what acc holds; the device never resets acc, the
+ * caller clears it.  A data-parallel reader sums columns 0-3 and maximises
+ * columns 4-7 over ranks.
+ * An env whose group id is >= G touches no memory outside the buffers and
+ * joins no group; its length_carry advances all the same, and it is counted
+ * once per call in *bad_envs (device int32, nullable, accumulated).
+ * Two launches, no host synchronisation.  ACMI_ERR_ARG before anything is
+ * enqueued: a null required pointer, N < 1, T < 1, G outside 1..64. */
+int64_t acmi_epstats_ws_doubles(int64_t N);
+int acmi_epstats_update(const float* episode_rewards, /* [N][T] f32, a NaN = no episode ended here */
+                        const uint8_t* groups,         /* [N], as acmi_retnorm_scan's */
+                        int N, int T, int G,
+                        int32_t* length_carry,         /* [N] steps of the running episode, starts 0 */
+                        double* ws, double* acc,       /* acc: [G][8] f64, accumulated in place */
+                        int32_t* bad_envs,             /* nullable, accumulated */
+                        acmi_stream_t stream);
+
 /* ------------------------------------------------------------------------
  * A2C losses and their gradient w.r.t. the head outputs.  Replaces
  * objectives.py:132-154 and the head part of tf.gradients of

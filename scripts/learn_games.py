@@ -21,6 +21,11 @@ overwritten in place with the evaluation batch's and put back, so --eval-envs mu
 --normalize-returns trains with the rewards scaled by the running std of the discounted return,
 per game (actorcritic.return_norm); every line of a point then holds "inv", the scale per game.
 
+--episode-stats keeps the training envs' episode statistics on the device (actorcritic.episode_stats) and
+appends to every line of a point "train_episodes": count, return mean / std / min / max and length mean /
+min / max of the TRAINING episodes that ended since the previous point (a mixed run: of the line's game).
+With --run-state they travel with the run state.
+
 --checkpoint-dir DIR keeps checkpoints (every --checkpoint-every updates, default --every, and at the
 end) under DIR/seed<seed>, and a later call with the same arguments goes on from the newest one up to
 --updates.  With --run-state every checkpoint carries the run state and the continuation
@@ -50,7 +55,8 @@ def run(args, seed, emit):
     N, T, E = args.envs, args.steps, args.episodes
     head = dict(algo=args.algo, game=args.game, seed=seed, envs=N, steps=T, eval_envs=args.eval_envs, eval_episodes=E,
                 episodic_life=args.episodic_life, max_episode_steps=args.max_episode_steps,
-                mask_actions=args.mask_actions, normalize_returns=args.normalize_returns)
+                mask_actions=args.mask_actions, normalize_returns=args.normalize_returns,
+                **(dict(episode_stats=True) if args.episode_stats else {}))
     eval_games = [g for g in GAMES if g in args.game.split('+')]
     mixed = len(eval_games) > 1
     # the head of the trained model: the mixed batch's (4) or the full set under masks (18)
@@ -85,6 +91,11 @@ def run(args, seed, emit):
         from actorcritic.envs.games.host import env_game_ids
         from actorcritic.return_norm import ReturnNormalizer
         norm = ReturnNormalizer(env_game_ids(args.game, N), num_groups=len(GAMES), group_names=GAMES)
+    ep_stats = None
+    if args.episode_stats:  # built here and handed to the example (no summary path: it never reads them)
+        from actorcritic.envs.games.host import env_game_ids
+        from actorcritic.episode_stats import EpisodeStats
+        ep_stats = EpisodeStats(env_game_ids(args.game, N), num_groups=len(GAMES), group_names=GAMES)
     t0 = time.perf_counter()
 
     def play(model, g):
@@ -106,19 +117,23 @@ def run(args, seed, emit):
             train_s = time.perf_counter() - t0
             inv = {} if not norm else dict(inv={n: round(float(v), 4) for n, v in
                                                     zip(norm.group_names, norm.inv.cpu().tolist())})
+            interval = ep_stats.read() if ep_stats is not None else None
             for g in eval_games:
+                train = {} if interval is None else dict(train_episodes={
+                    k: (None if v != v else v if isinstance(v, int) else round(float(v), 4))
+                    for k, v in interval[g if mixed else 'all'].items()})
                 emit(dict(head, policy='sampled' if args.sample else 'greedy', updates=updates,
                           env_steps=updates * N * T, wall_s=round(train_s, 2), **tag(g), **inv,
-                          **stats(play(model, g))))
+                          **stats(play(model, g)), **train))
 
     if args.algo == 'ppo':
         train_ppo(args.game, N, T, ckpt_dir, args.game, max_updates=args.updates - start, seed=seed, game=args.game,
-                  on_update=on_update, mask_actions=args.mask_actions, normalize_returns=norm, **rules, **fused,
-                  **keep)
+                  on_update=on_update, mask_actions=args.mask_actions, normalize_returns=norm,
+                  episode_stats=ep_stats, **rules, **fused, **keep)
     else:
         train_a2c_acktr(args.algo == 'acktr', args.game, N, T, ckpt_dir, args.game, max_updates=args.updates - start,
                         seed=seed, game=args.game, on_update=on_update, mask_actions=args.mask_actions,
-                        normalize_returns=norm, **rules, **fused, **keep)
+                        normalize_returns=norm, episode_stats=ep_stats, **rules, **fused, **keep)
 
 
 def main():
@@ -142,6 +157,8 @@ def main():
                     help='scale rewards by the running std of the discounted return, per game')
     ap.add_argument('--fused-games', action='store_true',
                     help='train through the rollout\'s fused step (DeviceGameEnvs(fused_step=True))')
+    ap.add_argument('--episode-stats', action='store_true',
+                    help='append the training episodes\' statistics since the previous point to every line')
     ap.add_argument('--checkpoint-dir', default=None,
                     help='keep checkpoints under DIR/seed<seed> and go on from the newest one')
     ap.add_argument('--checkpoint-every', type=int, default=None, help='updates between checkpoints (default: --every)')
