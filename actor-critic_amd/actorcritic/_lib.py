@@ -135,6 +135,13 @@ _SIGS = {
     # episode statistics per group: (episode rewards, groups, N, T, G, length carry, ws, acc, bad_envs nullable)
     'acmi_epstats_ws_doubles': (c_i64, [c_i64]),
     'acmi_epstats_update': (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    # update diagnostics: value (values, targets, groups, N, T, G, ws, acc, bad_envs), policy (old, ld, new, ld,
+    # legal, groups, N, T, A, G, ws, acc, bad_envs, bad_rows), segments (x, y, offsets, S, ws, out)
+    'acmi_diag_ws_doubles': (c_i64, [c_i64, c_i64]),
+    'acmi_diag_value': (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp]),
+    'acmi_diag_policy': (c_int, [c_vp, c_int, c_vp, c_int, c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp,
+                                 c_vp, c_vp, c_vp]),
+    'acmi_diag_segments': (c_int, [c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_vp]),
     'acmi_a2c_loss_ws_floats': (c_i64, [c_int]),
     'acmi_a2c_loss': (c_int, [c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_float, c_float, c_float,
                               c_vp, c_int, c_vp, c_vp, c_vp]),

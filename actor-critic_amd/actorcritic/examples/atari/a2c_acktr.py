@@ -26,7 +26,8 @@ from actorcritic.session import Session, get_or_create_global_step, no_op
 def train_a2c_acktr(acktr, env_id, num_envs, num_steps, checkpoint_path, model_name, summary_path=None,
                     max_updates=None, seed=0, log_every=10, env_fns=None, mask_actions=False, game=None,
                     on_update=None, episodic_life=False, max_episode_steps=None, normalize_returns=False,
-                    fused_games=False, run_state=False, checkpoint_every=100, episode_stats=False):
+                    fused_games=False, run_state=False, checkpoint_every=100, episode_stats=False,
+                    diagnostics=False):
     """Trains an Atari model with A2C (RMSProp, conv3 64) or ACKTR (K-FAC, conv3 32).
 
     ``num_envs`` is per GPU; with WORLD_SIZE > 1 (torchrun) every rank steps its own shard.
@@ -70,6 +71,11 @@ def train_a2c_acktr(acktr, env_id, num_envs, num_steps, checkpoint_path, model_n
     with the run state.  Without a ``summary_path`` the loop never reads: the statistics gather until the
     caller does (scripts/learn_games.py reads them at its evaluation points).  Off (default):
     ``episode_reward`` is the last rollout's mean on rank 0, as ever.
+    ``diagnostics`` (``--diagnostics``): update diagnostics (actorcritic.update_diag; an UpdateDiagnostics of the
+    caller's own is taken as it is).  With a ``summary_path`` (given to every rank) the loop arms the object on
+    the updates that log, every rank reads it (a collective) and rank 0's log line gains ``explained_variance``,
+    ``policy_kl``, ``grad_norm``, ``step_norm``, ... (per layer, per game, and with ACKTR ``precon_*`` and
+    ``kfac_coeff``).  The run itself stays bit for bit the run without the option; off (default): today's keys.
     """
     parallel.init_from_env()
     if game is None and (episodic_life or max_episode_steps is not None or fused_games):
@@ -93,7 +99,9 @@ def train_a2c_acktr(acktr, env_id, num_envs, num_steps, checkpoint_path, model_n
     read_stats = stats is not None and bool(summary_path)  # (every rank knows the path; rank 0 alone writes)
     normalizer = make_normalizer(normalize_returns, multi_env)
     objective = A2CObjective(model, discount_factor=0.99, entropy_regularization_strength=0.01,
-                             normalize_returns=normalizer)
+                             normalize_returns=normalizer, diagnostics=make_diagnostics(diagnostics, multi_env))
+    diag = objective.diagnostics
+    read_diag = diag is not None and bool(summary_path)  # (armed on every rank: read() is a collective)
 
     global_step = get_or_create_global_step()
     # 1e7 env-steps (4e7 frames) over the whole job; global steps = env-steps / batch
@@ -135,16 +143,19 @@ def train_a2c_acktr(acktr, env_id, num_envs, num_steps, checkpoint_path, model_n
                 }
                 if agent.last_truncations is not None:  # time limits keep their bootstrap (objectives.py)
                     feed_dict[model.truncations_placeholder] = agent.last_truncations
+                if read_diag and log_now:
+                    diag.request()
                 out = session.run(fetches, feed_dict=feed_dict, host=len(fetches) > 3)
                 step = global_step.value
                 updates += 1
+                diag_scalars = diag.read() if read_diag and log_now else {}
                 # episode statistics: the interval's, over all ranks -- a collective, so EVERY rank reads
                 interval = stats.read() if read_stats and log_now else None
                 if len(out) > 3:
                     episode_scalars = stats.log_scalars(interval) if read_stats else \
                         episode_reward_scalars(multi_env.batched, episode_rewards)
                     summary_writer.add(step, policy_loss=float(out[3]), baseline_loss=float(out[4]),
-                                       policy_entropy=float(out[5]), **episode_scalars)
+                                       policy_entropy=float(out[5]), **episode_scalars, **diag_scalars)
                 if on_update is not None:
                     on_update(updates, model)
                 if checkpoint_path is not None and step % checkpoint_every == 0 and step > 0:
@@ -162,6 +173,15 @@ def train_a2c_acktr(acktr, env_id, num_envs, num_steps, checkpoint_path, model_n
             if summary_writer is not None:
                 summary_writer.close()
     return model, optimizer
+
+
+def make_diagnostics(diagnostics, multi_env):
+    """``diagnostics`` of the train functions -> None (falsy), the caller's UpdateDiagnostics, or (True) one
+    with the groups of the envs."""
+    from actorcritic.update_diag import UpdateDiagnostics
+    if isinstance(diagnostics, UpdateDiagnostics):
+        return diagnostics
+    return UpdateDiagnostics.for_envs(multi_env) if diagnostics else None
 
 
 def make_normalizer(normalize_returns, multi_env):
@@ -308,5 +328,6 @@ if __name__ == '__main__':
                                        if '--max-episode-steps' in argv else None),
                     normalize_returns='--normalize-returns' in argv, fused_games='--fused-games' in argv,
                     run_state='--run-state' in argv, episode_stats='--episode-stats' in argv,
+                    diagnostics='--diagnostics' in argv,
                     checkpoint_every=(int(argv[argv.index('--checkpoint-every') + 1])
                                       if '--checkpoint-every' in argv else 100))

@@ -20,7 +20,7 @@ from actorcritic.envs.atari.model import AtariModel
 from actorcritic.examples.atari.a2c_acktr import (check_run_state_args, create_environments,
                                                   create_game_environments, create_host_environments,
                                                   episode_reward_scalars, load_model, load_run_state,
-                                                  make_normalizer, save_checkpoint, save_model)
+                                                  make_diagnostics, make_normalizer, save_checkpoint, save_model)
 from actorcritic.multi_env import MultiEnv
 from actorcritic.nn import AdamOptimizer, ClipGlobalNormOptimizer, linear_decay
 from actorcritic.objectives import PPOObjective
@@ -31,7 +31,7 @@ def train_ppo(env_id, num_envs, num_steps, checkpoint_path, model_name, summary_
               log_every=10, num_epochs=4, num_minibatches=4, clip_range=0.1, value_clip_range=None,
               minibatch='envs', env_fns=None, mask_actions=False, game=None, on_update=None, episodic_life=False,
               max_episode_steps=None, normalize_returns=False, fused_games=False, run_state=False,
-              checkpoint_every=100, episode_stats=False):
+              checkpoint_every=100, episode_stats=False, diagnostics=False):
     """Trains an Atari model (conv3 64) with PPO.
 
     ``num_envs`` is per GPU; with WORLD_SIZE > 1 (torchrun) every rank steps its own shard.
@@ -48,6 +48,8 @@ def train_ppo(env_id, num_envs, num_steps, checkpoint_path, model_name, summary_
     ``on_update``, ``normalize_returns`` (``--normalize-returns``), ``fused_games`` (``--fused-games``),
     ``run_state`` (``--run-state``), ``checkpoint_every`` (``--checkpoint-every K``) and ``episode_stats``
     (``--episode-stats``): as in a2c_acktr.train_a2c_acktr.
+    ``diagnostics`` (``--diagnostics``): as there; the step and the KL are those of the whole op (all epochs),
+    the gradient is the last minibatch's.
     """
     parallel.init_from_env()
     if game is None and (episodic_life or max_episode_steps is not None or fused_games):
@@ -71,7 +73,10 @@ def train_ppo(env_id, num_envs, num_steps, checkpoint_path, model_name, summary_
     normalizer = make_normalizer(normalize_returns, multi_env)
     objective = PPOObjective(model, discount_factor=0.99, entropy_regularization_strength=0.01,
                              clip_range=clip_range, value_clip_range=value_clip_range, gae_lambda=0.95,
-                             normalize_advantages=True, normalize_returns=normalizer)
+                             normalize_advantages=True, normalize_returns=normalizer,
+                             diagnostics=make_diagnostics(diagnostics, multi_env))
+    diag = objective.diagnostics
+    read_diag = diag is not None and bool(summary_path)  # (armed on every rank: read() is a collective)
 
     global_step = get_or_create_global_step()
     # 1e7 env-steps (4e7 frames) over the whole job; global steps = env-steps / batch
@@ -113,9 +118,12 @@ def train_ppo(env_id, num_envs, num_steps, checkpoint_path, model_name, summary_
                 }
                 if agent.last_truncations is not None:  # time limits keep their bootstrap (objectives.py)
                     feed_dict[model.truncations_placeholder] = agent.last_truncations
+                if read_diag and log_now:
+                    diag.request()
                 out = session.run(fetches, feed_dict=feed_dict, host=len(fetches) > 3)
                 step = global_step.value
                 updates += 1
+                diag_scalars = diag.read() if read_diag and log_now else {}
                 # episode statistics: the interval's, over all ranks -- a collective, so EVERY rank reads
                 interval = stats.read() if read_stats and log_now else None
                 if len(out) > 3:
@@ -123,7 +131,7 @@ def train_ppo(env_id, num_envs, num_steps, checkpoint_path, model_name, summary_
                         episode_reward_scalars(multi_env.batched, episode_rewards)
                     summary_writer.add(step, policy_loss=float(out[3]), baseline_loss=float(out[4]),
                                        policy_entropy=float(out[5]), approx_kl=float(out[6]),
-                                       clip_fraction=float(out[7]), **episode_scalars)
+                                       clip_fraction=float(out[7]), **episode_scalars, **diag_scalars)
                 if on_update is not None:
                     on_update(updates, model)
                 if checkpoint_path is not None and step % checkpoint_every == 0 and step > 0:
@@ -166,5 +174,6 @@ if __name__ == '__main__':
                                  if '--max-episode-steps' in argv else None),
               normalize_returns='--normalize-returns' in argv, fused_games='--fused-games' in argv,
               run_state='--run-state' in argv, episode_stats='--episode-stats' in argv,
+              diagnostics='--diagnostics' in argv,
               checkpoint_every=(int(argv[argv.index('--checkpoint-every') + 1])
                                 if '--checkpoint-every' in argv else 100))

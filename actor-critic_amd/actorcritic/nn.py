@@ -50,8 +50,25 @@ class OptimizeOp(Node):
             raise NotImplementedError('only the shared A2C loss (objective.optimize_shared) is differentiable '
                                       'on this engine')
         ctx.eval(self.loss)
+        # update diagnostics (actorcritic.update_diag; opt-in, armed for single updates): the value
+        # statistics and a copy of the parameters before the update, the rest after it
+        diag = getattr(objective, 'diagnostics', None)
+        armed = diag is not None and diag.armed
+        if armed:
+            eng = objective.model.engine
+            st = ctx.eval(objective._targets_node)
+            diag.before_update(eng, st.fwd, st)
         self.optimizer._update(ctx, objective, self.global_step)
+        if armed:
+            diag.after_update(eng, st.fwd, st.grads, _innermost(self.optimizer))
         return None
+
+
+def _innermost(optimizer):
+    """The optimizer a ClipGlobalNormOptimizer (or a chain of them) wraps."""
+    while hasattr(optimizer, '_optimizer'):
+        optimizer = optimizer._optimizer
+    return optimizer
 
 
 class Optimizer(object):

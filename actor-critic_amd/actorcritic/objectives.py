@@ -158,6 +158,13 @@ def _check_normalizer(normalize_returns):
     return normalize_returns
 
 
+def _check_diagnostics(diagnostics):
+    from actorcritic.update_diag import UpdateDiagnostics
+    if diagnostics is not None and not isinstance(diagnostics, UpdateDiagnostics):
+        raise TypeError('diagnostics takes an UpdateDiagnostics or None, got {!r}'.format(diagnostics))
+    return diagnostics
+
+
 def _normalize_advantages(eng, adv, M, eps):
     """adv <- (adv - mean) / (std + eps) over the global batch (all ranks)."""
     ws = getattr(eng, '_adv_ws', None)
@@ -229,11 +236,14 @@ class A2CObjective(ActorCriticObjective):
     """A2C/ACKTR objective (objectives.py:82-175)."""
 
     def __init__(self, model, discount_factor=0.99, entropy_regularization_strength=0.01, name=None,
-                 gae_lambda=None, normalize_advantages=False, advantage_epsilon=1e-8, normalize_returns=None):
+                 gae_lambda=None, normalize_advantages=False, advantage_epsilon=1e-8, normalize_returns=None,
+                 diagnostics=None):
         """The reference's arguments (objectives.py:100); ``gae_lambda`` (None: the
-        reference's n-step targets; a float in [0, 1]: GAE(lambda)), ``normalize_advantages``
-        and ``normalize_returns`` (a :class:`actorcritic.return_norm.ReturnNormalizer`) are
-        extensions beyond it (module docstring)."""
+        reference's n-step targets; a float in [0, 1]: GAE(lambda)), ``normalize_advantages``,
+        ``normalize_returns`` (a :class:`actorcritic.return_norm.ReturnNormalizer`) and
+        ``diagnostics`` (a :class:`actorcritic.update_diag.UpdateDiagnostics`: the optimize op
+        records an update's diagnostics whenever the object is armed) are extensions beyond it
+        (module docstring)."""
         if gae_lambda is not None and not 0.0 <= float(gae_lambda) <= 1.0:
             raise ValueError('gae_lambda must be in [0, 1] or None, got {}'.format(gae_lambda))
         self._model = model
@@ -241,6 +251,7 @@ class A2CObjective(ActorCriticObjective):
         self._gae_lambda = None if gae_lambda is None else float(gae_lambda)
         self._normalize = bool(normalize_advantages)
         self._retnorm = _check_normalizer(normalize_returns)
+        self.diagnostics = _check_diagnostics(diagnostics)
         self._adv_eps = float(advantage_epsilon)
         self._beta = float(entropy_regularization_strength)
         self._vcoef = 0.5
@@ -465,7 +476,7 @@ class PPOObjective(ActorCriticObjective):
 
     def __init__(self, model, discount_factor=0.99, entropy_regularization_strength=0.01, clip_range=0.1,
                  value_clip_range=None, gae_lambda=0.95, normalize_advantages=True, advantage_epsilon=1e-8,
-                 name=None, normalize_returns=None):
+                 name=None, normalize_returns=None, diagnostics=None):
         if not float(clip_range) > 0.0:
             raise ValueError('clip_range must be positive, got {}'.format(clip_range))
         if value_clip_range is not None and not float(value_clip_range) > 0.0:
@@ -482,6 +493,7 @@ class PPOObjective(ActorCriticObjective):
         self._normalize_minibatch = normalize_advantages == 'minibatch'
         self._normalize = not self._normalize_minibatch and bool(normalize_advantages)
         self._retnorm = _check_normalizer(normalize_returns)
+        self.diagnostics = _check_diagnostics(diagnostics)  # (A2CObjective's; the whole op's step and KL)
         self._adv_eps = float(advantage_epsilon)
         self._beta = float(entropy_regularization_strength)
         self._clip = float(clip_range)
@@ -626,10 +638,18 @@ class PPOOptimizeOp(Node):
         eng = obj._model.engine
         run = ctx.eval(obj._batch_node)
         step = self.global_step.value if self.global_step is not None else self._runs
+        # update diagnostics (actorcritic.update_diag): of the whole op -- the step and the KL over all
+        # epochs, the value statistics of the batch's forward; the gradient is the last minibatch's
+        diag = obj.diagnostics if obj.diagnostics is not None and obj.diagnostics.armed else None
+        if diag is not None:
+            diag.before_update(eng, run.fwd, run.st)
         if self.minibatch == 'rows':
             st = self._epochs_of_rows(ctx, run, step)
         else:
             st = self._epochs_of_env_slices(ctx, run, step)
+        if diag is not None:
+            from actorcritic.nn import _innermost
+            diag.after_update(eng, run.fwd, st.grads, _innermost(self.optimizer))
         if eng.collective:  # (the other four scalars travel with the gradients)
             from actorcritic import parallel
             parallel.allreduce_sum_(run.bufs.clip_frac, force=True)

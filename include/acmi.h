@@ -374,6 +374,67 @@ int acmi_epstats_update(const float* episode_rewards, /* [N][T] f32, a NaN = no 
                         int32_t* bad_envs,             /* nullable, accumulated */
                         acmi_stream_t stream);
 
+/* Update diagnostics (an option beyond the reference): what one parameter update
+ * did, as double accumulators per group of envs (per game) that a log line reads
+ * with one copy.  Rows are env-major [N][T]: row m belongs to env m / T.
+ * groups[N] u8 is nullable (NULL: every env in group 0); G in 1..64.  An env
+ * whose group id is >= G adds nothing and is counted once per call in *bad_envs
+ * (device int32, nullable, accumulated).  Every call OVERWRITES its output;
+ * nothing carries over between calls.  Every sum is formed in double in an
+ * order that the arguments alone fix (partials in ws, one reducing kernel; no
+ * floating-point atomics): same bytes in, same bytes out.  Two launches per
+ * call, no host synchronisation.  ws: acmi_diag_ws_doubles(M, S) doubles serve
+ * any of the three calls over M = N*T rows / S segments (calls that share one
+ * ws must be ordered on one stream).
+ *
+ * acmi_diag_value: acc[g] = (n, sum v, sum y, sum y^2, sum e, sum e^2) over the
+ *   rows of group g, v = (double)values[m], y = (double)targets[m], e = y - v
+ *   (rounded to double), e^2 rounded before it is added.  The explained variance
+ *   1 - Var(e)/Var(y) is the reader's to derive.
+ * acmi_diag_policy: acc[g] = (n, sum KL(old||new), sum H(new), max KL) over the
+ *   GOOD rows of group g; the maximum starts at -inf.  legal: one uint32 word per
+ *   row (nullable; bit a set = action a is legal, bits at or above A ignored), the
+ *   meaning the *_masked entry points give it: every sum below runs over the
+ *   legal set S only, an illegal logit influences nothing.  Per row and matrix,
+ *   in double from the float32 logits z: mx = max_S z, lse = mx + log(sum_S
+ *   exp(z - mx)), logp = z - lse, p = exp(logp), all in ascending action order;
+ *   KL = sum_S round(p_old (logp_old - logp_new)), H = -sum_S round(p_new logp_new).
+ *   A row is BAD when S is empty or any of its A logits, in either matrix, is
+ *   not finite; a bad row adds nothing and counts in *bad_rows (device int32,
+ *   nullable, accumulated), whatever its env's group.  A in 1..64 without legal,
+ *   1..32 with it; ld_old, ld_new >= A.
+ * acmi_diag_segments: out[s] = (sum x^2, sum y^2, sum x y, sum (x - y)^2) over the
+ *   elements [offsets[s], offsets[s+1]) of x and y, products and the difference
+ *   formed in double ((x - y)^2 rounded before it is added).  y is nullable and
+ *   then counts as zero.  offsets: device int64 [S + 1], non-decreasing (the
+ *   CALLER checks that: the entry point never reads them on the host); an empty
+ *   segment gives zeros.  A segment is cut into 64 slices whose length follows
+ *   from its two offsets alone, never from the grid.  S in 1..65535.
+ *
+ * ACMI_ERR_ARG before anything is enqueued: a null required pointer (values,
+ * targets, logits_old, logits_new, x, offsets, ws, acc / out), N < 1, T < 1,
+ * N*T >= 2^31, G outside 1..64, A or ld_* out of range, S outside 1..65535. */
+int64_t acmi_diag_ws_doubles(int64_t M, int64_t S);
+int acmi_diag_value(const float* values, const float* targets, /* [N][T] f32 each */
+                    const uint8_t* groups,                      /* [N], nullable */
+                    int N, int T, int G,
+                    double* ws, double* acc,                    /* acc: [G][6] f64, overwritten */
+                    int32_t* bad_envs,                          /* nullable, accumulated */
+                    acmi_stream_t stream);
+int acmi_diag_policy(const float* logits_old, int ld_old,      /* [N*T][ld_old] f32 */
+                     const float* logits_new, int ld_new,      /* [N*T][ld_new] f32 */
+                     const uint32_t* legal,                     /* [N*T], nullable */
+                     const uint8_t* groups,                     /* [N], nullable */
+                     int N, int T, int A, int G,
+                     double* ws, double* acc,                   /* acc: [G][4] f64, overwritten */
+                     int32_t* bad_envs, int32_t* bad_rows,      /* nullable, accumulated */
+                     acmi_stream_t stream);
+int acmi_diag_segments(const float* x, const float* y,         /* y nullable: zeros */
+                       const int64_t* offsets,                  /* device int64 [S + 1] */
+                       int S,
+                       double* ws, double* out,                 /* out: [S][4] f64, overwritten */
+                       acmi_stream_t stream);
+
 /* ------------------------------------------------------------------------
  * A2C losses and their gradient w.r.t. the head outputs.  Replaces
  * objectives.py:132-154 and the head part of tf.gradients of

@@ -26,6 +26,10 @@ appends to every line of a point "train_episodes": count, return mean / std / mi
 min / max of the TRAINING episodes that ended since the previous point (a mixed run: of the line's game).
 With --run-state they travel with the run state.
 
+--diagnostics records the update diagnostics (actorcritic.update_diag) of the update that ends at every point --
+explained variance, the step's KL, gradient / step norms and, with ACKTR, the preconditioner's cosines and the
+trust-region coefficient -- and appends them to the point's lines as "diagnostics".  The run itself is unchanged.
+
 --checkpoint-dir DIR keeps checkpoints (every --checkpoint-every updates, default --every, and at the
 end) under DIR/seed<seed>, and a later call with the same arguments goes on from the newest one up to
 --updates.  With --run-state every checkpoint carries the run state and the continuation
@@ -96,6 +100,14 @@ def run(args, seed, emit):
         from actorcritic.envs.games.host import env_game_ids
         from actorcritic.episode_stats import EpisodeStats
         ep_stats = EpisodeStats(env_game_ids(args.game, N), num_groups=len(GAMES), group_names=GAMES)
+    diag = None
+    point = lambda u: u % args.every == 0 or u == args.updates
+    if args.diagnostics:  # built here and armed here, for the update that ends at a point (no summary path)
+        from actorcritic.envs.games.host import env_game_ids
+        from actorcritic.update_diag import UpdateDiagnostics
+        diag = UpdateDiagnostics(env_game_ids(args.game, N), num_groups=len(GAMES), group_names=GAMES)
+        if point(start + 1):
+            diag.request()
     t0 = time.perf_counter()
 
     def play(model, g):
@@ -112,7 +124,14 @@ def run(args, seed, emit):
 
     def on_update(updates, model):
         updates += start  # (of the whole run: the example counts this call's)
-        if updates % args.every == 0 or updates == args.updates:
+        update_diag = {}
+        if diag is not None:
+            if point(updates):
+                update_diag = dict(diagnostics={k: (None if v != v else float('{:.6g}'.format(v)))
+                                                for k, v in diag.read().items()})
+            if point(updates + 1):
+                diag.request()
+        if point(updates):
             torch.cuda.synchronize()
             train_s = time.perf_counter() - t0
             inv = {} if not norm else dict(inv={n: round(float(v), 4) for n, v in
@@ -124,16 +143,17 @@ def run(args, seed, emit):
                     for k, v in interval[g if mixed else 'all'].items()})
                 emit(dict(head, policy='sampled' if args.sample else 'greedy', updates=updates,
                           env_steps=updates * N * T, wall_s=round(train_s, 2), **tag(g), **inv,
-                          **stats(play(model, g)), **train))
+                          **stats(play(model, g)), **train, **update_diag))
 
     if args.algo == 'ppo':
         train_ppo(args.game, N, T, ckpt_dir, args.game, max_updates=args.updates - start, seed=seed, game=args.game,
                   on_update=on_update, mask_actions=args.mask_actions, normalize_returns=norm,
-                  episode_stats=ep_stats, **rules, **fused, **keep)
+                  episode_stats=ep_stats, diagnostics=diag or False, **rules, **fused, **keep)
     else:
         train_a2c_acktr(args.algo == 'acktr', args.game, N, T, ckpt_dir, args.game, max_updates=args.updates - start,
                         seed=seed, game=args.game, on_update=on_update, mask_actions=args.mask_actions,
-                        normalize_returns=norm, episode_stats=ep_stats, **rules, **fused, **keep)
+                        normalize_returns=norm, episode_stats=ep_stats, diagnostics=diag or False, **rules, **fused,
+                        **keep)
 
 
 def main():
@@ -159,6 +179,8 @@ def main():
                     help='train through the rollout\'s fused step (DeviceGameEnvs(fused_step=True))')
     ap.add_argument('--episode-stats', action='store_true',
                     help='append the training episodes\' statistics since the previous point to every line')
+    ap.add_argument('--diagnostics', action='store_true',
+                    help='append the update diagnostics of the update that ends at a point to its lines')
     ap.add_argument('--checkpoint-dir', default=None,
                     help='keep checkpoints under DIR/seed<seed> and go on from the newest one')
     ap.add_argument('--checkpoint-every', type=int, default=None, help='updates between checkpoints (default: --every)')
