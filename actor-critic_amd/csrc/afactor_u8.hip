@@ -226,8 +226,12 @@ __global__ __launch_bounds__(256) void conv1_afactor_i8_kernel(const uint8_t* ob
 // Weight-gradient arithmetic: f16x2 (f16x2.hpp) -- d1 scaled by the power of two
 // of max |d1| (published by conv2's input-gradient epilogue, d1max) and split
 // into f16 h, l at the commit; the patch bytes u enter as the f16 subnormals
-// u * 2^-24 (exact; tower.hpp u8x8_to_f16); two MFMAs per k16 and tile, the
+// u * 2^-24 (exact; f16x2.hpp u8x8_to_f16); two MFMAs per k16 and tile, the
 // partials unscaled by 2^24 / s when stored.  Integer A partials are exact.
+// The weight gradient is f32-class where bright bytes carry the sum; the MFMA
+// adder holds a subnormal byte u to about 14 + log2(u) bits, so a batch lit only
+// by bytes below ~8 is held to 3e-5 .. 1e-4 of the gradient's range
+// (u8x8_to_f16's comment has the measurements).
 __device__ __forceinline__ void af_transpose4(uint32_t w0, uint32_t w1, uint32_t w2, uint32_t w3,
                                               uint32_t* out) {
   const uint32_t p01l = __builtin_amdgcn_perm(w1, w0, 0x05010400u);

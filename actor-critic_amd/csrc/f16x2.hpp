@@ -71,7 +71,18 @@ __device__ __forceinline__ f16x8 as_f16x8(const uint4& u) { return __builtin_bit
 
 // eight u8 pixels n as the f16 SUBNORMALS n * 2^-24 (exact; one byte permute per
 // two: the byte is the significand, the exponent field zero) -- the products'
-// 2^-24 is taken out with the other operand's scale when they are stored
+// 2^-24 is taken out with the other operand's scale when they are stored.
+// Every product is exact, but the MFMA's adder does not normalise a subnormal
+// operand: it aligns the 16 products and C on their exponent FIELDS and keeps a
+// fixed window below the largest, so a byte n spends its leading zero bits inside
+// that window.  Measured on gfx950 (one product beside one 2^k times larger in the
+// same MFMA): n = 255 keeps it to k = 16 and beyond, n = 16 to k = 16 (gone at 20),
+// n = 1 to k = 14 (gone at 16) -- a sum over bytes n carries about 14 + log2(n) bits
+// relative to its largest term where f32 carries 24.  Sums dominated by bright pixels
+// (game and Atari frames) are f32-class; a batch lit ONLY by bytes below ~8 is not:
+// conv1's weight gradient against float64, 24 images of bytes {0, n}, max-abs error
+// over range 1.2e-4 (n = 1), 2.6e-5 (n = 4), 6.5e-6 (n = 16), 1.3e-6 (n = 255) where
+// plain f32 gets 2e-6 .. 3e-6 at every n (tests/test_gpu_value_domain.py).
 __device__ __forceinline__ f16x8 u8x8_to_f16(uint2 u) {
   const uint32_t w0 = __builtin_amdgcn_perm(0u, u.x, 0x0c010c00u), w1 = __builtin_amdgcn_perm(0u, u.x, 0x0c030c02u);
   const uint32_t w2 = __builtin_amdgcn_perm(0u, u.y, 0x0c010c00u), w3 = __builtin_amdgcn_perm(0u, u.y, 0x0c030c02u);

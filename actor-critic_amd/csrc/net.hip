@@ -543,6 +543,17 @@ __global__ void sampled_head_grad_kernel(const float* logits, int ld, int B, int
   float* gr = g + (long long)m * ldg;
   for (int a = 0; a < A; ++a)
     gr[a] = legal_at<MASKED>(lg, a) ? expf(z[a] - mx) / se - (a == y ? 1.f : 0.f) : 0.f;
+  // The drawn action's column p_y - 1 carries p_y's rounding, 2^-24 absolute: on a
+  // saturated row that is 0 or one ulp of 1 where the column is 1e-8 .. 1e-30, and the
+  // policy head's G factor of a batch of such rows would be rounding noise.  Where the
+  // OTHER members hold less than 2^-7 of the sum (the subtraction would lose more
+  // than 7 of the 24 bits) the column is formed from them instead, -rest / se, to
+  // f32 relative accuracy.  Every other row keeps the subtraction (within 2^-17 of
+  // the column there), so runs whose policies are not saturated reproduce bit for bit.
+  float rest = 0.f;
+  for (int a = 0; a < A; ++a)
+    if (a != y && legal_at<MASKED>(lg, a)) rest += expf(z[a] - mx);
+  if (y >= 0 && rest > 0.f && rest < se * 0.0078125f) gr[y] = -rest / se;
   // Box-Muller from two further counters
   const float u1 = u01(mix32(h ^ 0x68e31da4U)) + (1.0f / 33554432.0f);
   const float u2 = u01(mix32(h ^ 0xb5297a4dU));

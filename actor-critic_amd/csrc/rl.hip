@@ -32,20 +32,35 @@ __global__ void sample_kernel(const float* logits, int ld, int B, int A, uint32_
   actions[m] = y;
 }
 
-// A row's log-sum-exp and entropy over its legal set S (all of 0..A-1 unmasked):
+// A row's log-softmax and entropy over its legal set S (all of 0..A-1 unmasked):
 //   mx = max_S z, se = sum_S expf(z - mx), lse = mx + logf(se), H = -sum_S p log p
 // in ascending a -- the one statement of the arithmetic every loss kernel shares.
+// log pi(a) = z[a] - lse while |mx| < 8: lse < 8 + log 64 there, so its rounding to
+// f32 puts at most half an ulp of 16, 1e-6, into a log-probability.  Past that the
+// rounding of lse grows with |mx| (5e-4 at logits near 1e4), and the maximum is
+// subtracted from the logit BEFORE the log of the sum, (z[a] - mx) - logf(se): the
+// difference z - mx is exact or rounded at its own size, and with se >= 1 (the
+// maximum's own term) log pi <= 0 and H >= 0 whatever the logits.  (One form for every
+// row would do; rows of ordinary logits keep the first so that runs reproduce bit for
+// bit.)
+struct RowLse {
+  float mx, lz, lse;  // the maximum over S, logf(se), their sum
+};
 template <bool MASKED>
-__device__ __forceinline__ float row_lse(const float* z, int A, uint32_t lg) {
+__device__ __forceinline__ RowLse row_lse(const float* z, int A, uint32_t lg) {
   const RowMaxSum ms = row_max_sum<MASKED>(z, A, lg);
-  return ms.mx + logf(ms.se);
+  const float lz = logf(ms.se);
+  return RowLse{ms.mx, lz, ms.mx + lz};
+}
+__device__ __forceinline__ float row_logp(float z, const RowLse& l) {
+  return fabsf(l.mx) < 8.f ? z - l.lse : (z - l.mx) - l.lz;
 }
 template <bool MASKED>
-__device__ __forceinline__ float row_entropy(const float* z, int A, uint32_t lg, float lse) {
+__device__ __forceinline__ float row_entropy(const float* z, int A, uint32_t lg, const RowLse& lse) {
   float H = 0.f;
   for (int a = 0; a < A; ++a) {
     if (!legal_at<MASKED>(lg, a)) continue;
-    const float lp = z[a] - lse;
+    const float lp = row_logp(z[a], lse);
     H -= expf(lp) * lp;
   }
   return H;
@@ -66,11 +81,11 @@ __global__ void categorical_kernel(const float* logits, int ld, int B, int A, co
   if (m >= B) return;
   const float* z = logits + (long long)m * ld;
   const uint32_t lg = MASKED ? legal_bits(legal[m], A) : 0xFFFFFFFFu;
-  const float lse = row_lse<MASKED>(z, A, lg);
+  const RowLse lse = row_lse<MASKED>(z, A, lg);
   if (ent) ent[m] = row_entropy<MASKED>(z, A, lg, lse);
   if (lpa && actions) {
     const int act = actions[m];
-    lpa[m] = action_ok<MASKED>(lg, act, A) ? z[act] - lse : -INFINITY;
+    lpa[m] = action_ok<MASKED>(lg, act, A) ? row_logp(z[act], lse) : -INFINITY;
   }
 }
 
@@ -371,7 +386,8 @@ constexpr int PPO_SUMS = 5;  // surrogate, entropy, value loss, old_logp - logp,
 // unclipped term is active, r = exp(lpa - old_logp)); with w = adv, PPO's columns
 // are A2C's bit for bit because they are these statements.
 struct RowPolicy {
-  float lse, H, lpa;
+  RowLse lse;
+  float H, lpa;
 };
 template <bool MASKED, class Weight>
 __device__ __forceinline__ RowPolicy policy_row(const float* z, int A, uint32_t lg, int act, float beta, float inv,
@@ -379,14 +395,14 @@ __device__ __forceinline__ RowPolicy policy_row(const float* z, int A, uint32_t 
   RowPolicy r;
   r.lse = row_lse<MASKED>(z, A, lg);
   r.H = row_entropy<MASKED>(z, A, lg, r.lse);
-  r.lpa = z[act] - r.lse;
+  r.lpa = row_logp(z[act], r.lse);
   const float w = weight(r.lpa);
   for (int a = 0; a < A; ++a) {
     if (!legal_at<MASKED>(lg, a)) {
       g[a] = 0.f;
       continue;
     }
-    const float lp = z[a] - r.lse;
+    const float lp = row_logp(z[a], r.lse);
     const float p = expf(lp);
     const float oh = a == act ? 1.f : 0.f;
     g[a] = -inv * (w * (oh - p) - beta * p * (lp + r.H));

@@ -136,7 +136,8 @@ FWD_NAMES = ('a1', 'a2', 'a3', 'a4', 'logits', 'value')
 
 
 def _stats_vs_float64(lib, cuda, B, params, seed=2024, A=4, C3=32, use_prep=True, masks=True, gemm_mode=None,
-                      forward_mode=None, conv_stats_mode=None, ldh=None, fill=0.0, zero_refs=None):
+                      forward_mode=None, conv_stats_mode=None, ldh=None, fill=0.0, zero_refs=None, obs=None,
+                      dhead=None, out=None):
     """One acmi_forward + acmi_backward (loss gradients + A factors) + one
     acmi_kfac_output_stats (G factors of the sampled losses) over B images of an
     (A, C3) net, each block against float64 (and against plain float32 arithmetic
@@ -151,11 +152,24 @@ def _stats_vs_float64(lib, cuda, B, params, seed=2024, A=4, C3=32, use_prep=True
     gradients, statistics and d1..d4 hold before the calls (NaN shows an entry left
     unwritten).  A block whose float64 reference is identically zero has no
     relative error: its key is appended to zero_refs (None: there must be none) and
-    its kernel error is 0 when the GPU block is exactly zero, inf otherwise."""
+    its kernel error is 0 when the GPU block is exactly zero, inf otherwise; the same
+    for a forward tensor whose float64 reference is identically zero.
+
+    obs: the [B,84,84,4] u8 images (None: uniformly random bytes drawn from seed);
+    dhead: the [B, A+1] f32 head gradients, copied into the zero-padded [B, ldh]
+    buffer (None: randn / B drawn from seed).  out: a dict that receives the raw
+    results -- 'acts' (the forward's a1..a4, logits, value), 'afac' / 'gfac' (the
+    factors as returned) and 'afac64' / 'gfac64' / 'fwd64' (the float64 references;
+    fwd64 of the first chunk of images)."""
     from actorcritic._engine import Layout
     L = Layout(A, C3)
     gen = torch.Generator(device=cuda).manual_seed(seed)
-    obs = torch.randint(0, 256, (B, 84, 84, 4), generator=gen, device=cuda, dtype=torch.uint8)
+    obs_rand = torch.randint(0, 256, (B, 84, 84, 4), generator=gen, device=cuda, dtype=torch.uint8)
+    if obs is None:  # (drawn either way: the generator's later draws do not depend on the hook)
+        obs = obs_rand
+    else:
+        assert obs.shape == (B, 84, 84, 4) and obs.dtype == torch.uint8, (obs.shape, obs.dtype)
+        obs = obs.to(cuda).contiguous()
     z = lambda *s: torch.zeros(*s, dtype=torch.float32, device=cuda)
     full = lambda *s: torch.full(s, fill, dtype=torch.float32, device=cuda)
     t = dict(a1=z(B, 20, 20, 32), a2=z(B, 9, 9, 64), a3=z(B, 7, 7, C3), a4=z(B, 512), logits=z(B, A), value=z(B))
@@ -174,8 +188,12 @@ def _stats_vs_float64(lib, cuda, B, params, seed=2024, A=4, C3=32, use_prep=True
     _lib.call('acmi_forward', ctypes.byref(net), _lib.ptr(obs), 84 * 84 * 4, B, ctypes.byref(acts), 1, st)
     # head gradients shaped like the A2C loss's (a2c_loss: mean over M rows)
     ldh = (A + 1 + 3) // 4 * 4 if ldh is None else ldh
+    dhead_in = dhead
     dhead = z(B, ldh)
     dhead[:, :A + 1] = torch.randn(B, A + 1, generator=gen, device=cuda) / B
+    if dhead_in is not None:
+        assert dhead_in.shape == (B, A + 1) and dhead_in.dtype == torch.float32, (dhead_in.shape, dhead_in.dtype)
+        dhead[:, :A + 1] = dhead_in.to(cuda)
     din = (ctypes.c_int64 * 6)()
     so = (ctypes.c_int64 * 11)()
     tot = ctypes.c_int64()
@@ -212,6 +230,7 @@ def _stats_vs_float64(lib, cuda, B, params, seed=2024, A=4, C3=32, use_prep=True
     chunk = 1024
     # the forward: max |GPU - float64| and max |plain f32 - float64| over the chunks
     fwd_max = {k: [0.0, 0.0, 0.0] for k in FWD_NAMES}
+    fwd_nz = {k: False for k in FWD_NAMES}  # the GPU tensor has a nonzero entry
     for i in range(0, B, chunk):
         j = min(B, i + chunk)
         outs = {}
@@ -224,6 +243,9 @@ def _stats_vs_float64(lib, cuda, B, params, seed=2024, A=4, C3=32, use_prep=True
             m[0] = max(m[0], (t[k][i:j].double().reshape(o64.shape) - o64).abs().max().item())
             m[1] = max(m[1], (o32.double() - o64).abs().max().item())
             m[2] = max(m[2], o64.abs().max().item())
+            fwd_nz[k] = fwd_nz[k] or t[k][i:j].any().item()
+        if out is not None and i == 0:
+            out['fwd64'] = dict(zip(FWD_NAMES, outs[ref]))
     g_ref, a_ref, gf_ref = ref.result()
     g_32, a_32, gf_32 = ref32.result()
 
@@ -245,8 +267,17 @@ def _stats_vs_float64(lib, cuda, B, params, seed=2024, A=4, C3=32, use_prep=True
         errs[('G', l)] = rel(('G', l), gstat[so[5 + l]:so[5 + l] + n * n].reshape(n, n), gf_ref[l], gf_32[l])
     for k in FWD_NAMES:
         e_gpu, e_32, m = fwd_max[k]
-        assert m > 0, ('fwd', k)
-        errs[('fwd', k)] = (e_gpu / m, e_32 / m)
+        if m == 0.0:
+            assert zero_refs is not None, (('fwd', k), 'the float64 reference is identically zero')
+            zero_refs.append(('fwd', k))
+            errs[('fwd', k)] = (float('inf') if fwd_nz[k] else 0.0, 0.0)
+        else:
+            errs[('fwd', k)] = (e_gpu / m, e_32 / m)
+    if out is not None:
+        out['acts'] = {k: t[k] for k in FWD_NAMES}
+        out['afac'] = [astat[so[f]:so[f] + din[f] ** 2].reshape(din[f], din[f]) for f in range(5)]
+        out['gfac'] = [gstat[so[5 + l]:so[5 + l] + nf[5 + l] ** 2].reshape(nf[5 + l], nf[5 + l]) for l in range(6)]
+        out['afac64'], out['gfac64'] = a_ref, gf_ref
     for k, (v, v32) in errs.items():
         print(k, 'kernel %.2e  plain f32 %.2e' % (v, v32))
     return errs
