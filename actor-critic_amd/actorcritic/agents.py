@@ -33,6 +33,8 @@ import torch
 
 from actorcritic import _lib, _ops
 from actorcritic._engine import OBS_BYTES
+from actorcritic.episode_stats import EpisodeStats
+from actorcritic.return_norm import own_or_for_envs
 
 
 class Agent(object, metaclass=ABCMeta):
@@ -145,15 +147,12 @@ class MultiEnvAgent(Agent):
         # the last rollout's truncations, [N, T] bool on the device (the feed of
         # model.truncations_placeholder); None for envs that emit none
         self.last_truncations = None
-        self.episode_stats = None
-        if episode_stats is not None and episode_stats is not False:
-            from actorcritic.episode_stats import EpisodeStats
-            self.episode_stats = EpisodeStats.for_envs(multi_env) if episode_stats is True else episode_stats
-            if not isinstance(self.episode_stats, EpisodeStats):
-                raise TypeError('episode_stats: an EpisodeStats or True, got {}'.format(type(episode_stats).__name__))
-            if self.episode_stats.num_envs != multi_env.num_envs:
-                raise ValueError('episode_stats of {} envs for an agent of {}'.format(self.episode_stats.num_envs,
-                                                                                   multi_env.num_envs))
+        if not isinstance(episode_stats, (EpisodeStats, bool, type(None))):
+            raise TypeError('episode_stats: an EpisodeStats or True, got {}'.format(type(episode_stats).__name__))
+        self.episode_stats = own_or_for_envs(episode_stats, EpisodeStats, multi_env)
+        if self.episode_stats is not None and self.episode_stats.num_envs != multi_env.num_envs:
+            raise ValueError('episode_stats of {} envs for an agent of {}'.format(self.episode_stats.num_envs,
+                                                                               multi_env.num_envs))
         if self._mask_actions:
             masks = getattr(getattr(multi_env, 'batched', None), 'legal_action_masks', None)
             if masks is None:

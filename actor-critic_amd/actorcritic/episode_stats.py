@@ -24,7 +24,7 @@ import numpy as np
 import torch
 
 from actorcritic import _lib
-from actorcritic.return_norm import MAX_GROUPS, groups_for_envs
+from actorcritic.return_norm import check_groups, groups_for_envs
 
 COLS = 8  # episodes, sum ret, sum ret^2, sum len | max ret, max -ret, max len, max -len
 NUM_SUMS = 4
@@ -117,18 +117,8 @@ class EpisodeStats(object):
     """
 
     def __init__(self, groups, num_groups=None, group_names=None):
-        ids = [int(g) for g in groups]
-        if not ids:
-            raise ValueError('groups: one id per env, got none')
-        G = max(ids) + 1 if num_groups is None else int(num_groups)
-        if not 1 <= G <= MAX_GROUPS:
-            raise ValueError('num_groups={} outside 1..{}'.format(G, MAX_GROUPS))
-        if min(ids) < 0 or max(ids) >= G:
-            raise ValueError('group ids must lie in 0..{}'.format(G - 1))
-        if group_names is not None and len(group_names) != G:
-            raise ValueError('group_names: {} names for {} groups'.format(len(group_names), G))
+        ids, G, self.group_names = check_groups(groups, num_groups, group_names)
         self.num_envs, self.num_groups = len(ids), G
-        self.group_names = None if group_names is None else tuple(str(n) for n in group_names)
         self.groups = torch.tensor(ids, dtype=torch.uint8)
         self.length_carry = torch.zeros(len(ids), dtype=torch.int32)
         self.acc = torch.from_numpy(cleared_acc(G))

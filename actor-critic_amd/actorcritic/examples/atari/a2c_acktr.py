@@ -1,9 +1,9 @@
 """A2C / ACKTR on Atari — the reference entry point (actorcritic/examples/atari/a2c_acktr.py)
 on the MI355X engine.  The structure is the reference's line for line: environments ->
 MultiEnv -> AtariModel -> MultiEnvAgent -> A2CObjective -> optimizer ->
-``optimize_shared`` -> a session loop that interacts and runs the optimize op.  The
-differences are the imports (no tensorflow / kfac / gym) and the synthetic batched
-Atari stepper in place of ALE subprocesses.
+``optimize_shared`` -> a session loop that interacts and runs the optimize op (loop.py,
+shared with ppo.py).  The differences are the imports (no tensorflow / kfac / gym) and the
+synthetic batched Atari stepper in place of ALE subprocesses.
 """
 
 import os
@@ -19,8 +19,8 @@ from actorcritic.kfac_utils import ColdStartPeriodicInvUpdateKfacOpt, LayerColle
 from actorcritic.multi_env import MultiEnv
 from actorcritic.nn import ClipGlobalNormOptimizer, MomentumOptimizer, RMSPropOptimizer, linear_decay
 from actorcritic.objectives import A2CObjective
-from actorcritic.return_norm import ReturnNormalizer
-from actorcritic.session import Session, get_or_create_global_step, no_op
+from actorcritic.return_norm import ReturnNormalizer, own_or_for_envs
+from actorcritic.session import get_or_create_global_step
 
 
 def train_a2c_acktr(acktr, env_id, num_envs, num_steps, checkpoint_path, model_name, summary_path=None,
@@ -77,31 +77,19 @@ def train_a2c_acktr(acktr, env_id, num_envs, num_steps, checkpoint_path, model_n
     ``policy_kl``, ``grad_norm``, ``step_norm``, ... (per layer, per game, and with ACKTR ``precon_*`` and
     ``kfac_coeff``).  The run itself stays bit for bit the run without the option; off (default): today's keys.
     """
+    # (loop.py calls the helpers below, so it is imported here, not at the top)
+    from actorcritic.examples.atari.loop import make_multi_env, train_loop
     parallel.init_from_env()
-    if game is None and (episodic_life or max_episode_steps is not None or fused_games):
-        raise ValueError('episodic_life, max_episode_steps and fused_games need a device game (game=)')
-    check_run_state_args(run_state, checkpoint_every, env_fns)
-    if game is not None:
-        multi_env = MultiEnv(create_game_environments(game, num_envs, seed=seed, full_action_set=mask_actions,
-                                                      episodic_life=episodic_life,
-                                                      max_episode_steps=max_episode_steps, fused_step=fused_games))
-    elif env_fns is not None:
-        multi_env = create_host_environments(env_fns)
-        num_envs = multi_env.num_envs
-    else:
-        multi_env = MultiEnv(create_environments(env_id, num_envs, seed=seed, full_action_set=mask_actions))
+    multi_env, num_envs = make_multi_env(env_id, num_envs, seed, env_fns, mask_actions, game, episodic_life,
+                                         max_episode_steps, fused_games, run_state, checkpoint_every)
 
     conv3_num_filters = 32 if acktr else 64
     model = AtariModel(multi_env.observation_space, multi_env.action_space, conv3_num_filters, random_seed=seed)
     agent = MultiEnvAgent(multi_env, model, num_steps, mask_actions=mask_actions,
                           episode_stats=episode_stats or None)
-    stats = agent.episode_stats
-    read_stats = stats is not None and bool(summary_path)  # (every rank knows the path; rank 0 alone writes)
-    normalizer = make_normalizer(normalize_returns, multi_env)
     objective = A2CObjective(model, discount_factor=0.99, entropy_regularization_strength=0.01,
-                             normalize_returns=normalizer, diagnostics=make_diagnostics(diagnostics, multi_env))
-    diag = objective.diagnostics
-    read_diag = diag is not None and bool(summary_path)  # (armed on every rank: read() is a collective)
+                             normalize_returns=make_normalizer(normalize_returns, multi_env),
+                             diagnostics=make_diagnostics(diagnostics, multi_env))
 
     global_step = get_or_create_global_step()
     # 1e7 env-steps (4e7 frames) over the whole job; global steps = env-steps / batch
@@ -113,65 +101,11 @@ def train_a2c_acktr(acktr, env_id, num_envs, num_steps, checkpoint_path, model_n
 
     optimizer = create_optimizer(acktr, model, learning_rate)
     optimize_op = objective.optimize_shared(optimizer, baseline_loss_weight=0.5, global_step=global_step)
-
-    summary_writer = checkpoint.ScalarLog(summary_path) if (summary_path and parallel.rank() == 0) else None
-    summary_op = no_op()
-
-    with Session() as session:
-        if checkpoint_path is not None:
-            if load_model(checkpoint_path, model, optimizer, global_step, objective) and run_state:
-                load_run_state(checkpoint_path, model_name, global_step.value, agent, objective)
-        step = global_step.value
-        updates = 0
-        saved_step = None
-        try:
-            while step < max_step and (max_updates is None or updates < max_updates):
-                observations, actions, rewards, terminals, next_observations, infos = agent.interact(session)
-                episode_rewards = wrappers.EpisodeInfoWrapper.get_episode_rewards_from_info_batch(infos) \
-                    if summary_writer is not None and stats is None else None
-                log_now = step % log_every == 0
-
-                fetches = [summary_op, global_step, optimize_op]
-                if summary_writer is not None and log_now:
-                    fetches += [objective.policy_loss, objective.baseline_loss, objective.mean_entropy]
-                feed_dict = {
-                    model.observations_placeholder: observations,
-                    model.bootstrap_observations_placeholder: next_observations,
-                    model.actions_placeholder: actions,
-                    model.rewards_placeholder: rewards,
-                    model.terminals_placeholder: terminals,
-                }
-                if agent.last_truncations is not None:  # time limits keep their bootstrap (objectives.py)
-                    feed_dict[model.truncations_placeholder] = agent.last_truncations
-                if read_diag and log_now:
-                    diag.request()
-                out = session.run(fetches, feed_dict=feed_dict, host=len(fetches) > 3)
-                step = global_step.value
-                updates += 1
-                diag_scalars = diag.read() if read_diag and log_now else {}
-                # episode statistics: the interval's, over all ranks -- a collective, so EVERY rank reads
-                interval = stats.read() if read_stats and log_now else None
-                if len(out) > 3:
-                    episode_scalars = stats.log_scalars(interval) if read_stats else \
-                        episode_reward_scalars(multi_env.batched, episode_rewards)
-                    summary_writer.add(step, policy_loss=float(out[3]), baseline_loss=float(out[4]),
-                                       policy_entropy=float(out[5]), **episode_scalars, **diag_scalars)
-                if on_update is not None:
-                    on_update(updates, model)
-                if checkpoint_path is not None and step % checkpoint_every == 0 and step > 0:
-                    save_checkpoint(checkpoint_path, model_name, step, model, optimizer, objective,
-                                    agent if run_state else None)
-                    saved_step = step
-            if run_state and checkpoint_path is not None and updates > 0 and saved_step != step:
-                save_checkpoint(checkpoint_path, model_name, step, model, optimizer, objective, agent)
-        except KeyboardInterrupt:
-            print('Stop requested')
-            if checkpoint_path is not None and parallel.rank() == 0 and not run_state:
-                save_model(checkpoint_path, model_name, step, model, optimizer, objective)
-        finally:
-            multi_env.close()
-            if summary_writer is not None:
-                summary_writer.close()
+    scalars = [('policy_loss', objective.policy_loss), ('baseline_loss', objective.baseline_loss),
+               ('policy_entropy', objective.mean_entropy)]
+    train_loop(multi_env, model, agent, objective, optimizer, optimize_op, global_step, max_step, scalars,
+               checkpoint_path, model_name, summary_path, max_updates, log_every, on_update, run_state,
+               checkpoint_every)
     return model, optimizer
 
 
@@ -179,17 +113,13 @@ def make_diagnostics(diagnostics, multi_env):
     """``diagnostics`` of the train functions -> None (falsy), the caller's UpdateDiagnostics, or (True) one
     with the groups of the envs."""
     from actorcritic.update_diag import UpdateDiagnostics
-    if isinstance(diagnostics, UpdateDiagnostics):
-        return diagnostics
-    return UpdateDiagnostics.for_envs(multi_env) if diagnostics else None
+    return own_or_for_envs(diagnostics, UpdateDiagnostics, multi_env)
 
 
 def make_normalizer(normalize_returns, multi_env):
     """``normalize_returns`` of the train functions -> None (falsy), the caller's ReturnNormalizer, or
     (True) one with the groups of the envs."""
-    if isinstance(normalize_returns, ReturnNormalizer):
-        return normalize_returns
-    return ReturnNormalizer.for_envs(multi_env) if normalize_returns else None
+    return own_or_for_envs(normalize_returns, ReturnNormalizer, multi_env)
 
 
 def create_environments(env_id, num_envs, seed=0, full_action_set=False):
@@ -311,23 +241,7 @@ def load_run_state(checkpoint_path, model_name, step, agent, objective=None):
 
 
 if __name__ == '__main__':
-    acktr = True
-    argv = sys.argv[1:]
-    game = argv[argv.index('--game') + 1] if '--game' in argv else None
-    env_id = 'BreakoutNoFrameskip-v4' if game is None else 'DeviceGame-' + game
-    num_envs = 32
-    num_steps = 20
-    results_path = os.path.abspath('./results')
-    checkpoint_path = results_path + '/checkpoints/' + env_id
-    summary_path = results_path + '/summaries/' + env_id
-    os.makedirs(checkpoint_path, exist_ok=True)
-    os.makedirs(summary_path, exist_ok=True)
-    train_a2c_acktr(acktr, env_id, num_envs, num_steps, checkpoint_path, 'Atari-' + env_id, summary_path,
-                    mask_actions='--mask-actions' in argv, game=game, episodic_life='--episodic-life' in argv,
-                    max_episode_steps=(int(argv[argv.index('--max-episode-steps') + 1])
-                                       if '--max-episode-steps' in argv else None),
-                    normalize_returns='--normalize-returns' in argv, fused_games='--fused-games' in argv,
-                    run_state='--run-state' in argv, episode_stats='--episode-stats' in argv,
-                    diagnostics='--diagnostics' in argv,
-                    checkpoint_every=(int(argv[argv.index('--checkpoint-every') + 1])
-                                      if '--checkpoint-every' in argv else 100))
+    from actorcritic.examples.atari.loop import parse_flags, result_paths
+    flags = parse_flags(sys.argv[1:])
+    env_id, checkpoint_path, summary_path = result_paths(flags['game'])
+    train_a2c_acktr(True, env_id, 32, 20, checkpoint_path, 'Atari-' + env_id, summary_path, **flags)

@@ -136,6 +136,29 @@ def groups_for_envs(batched_env):
     return [0] * N, 1, None
 
 
+def check_groups(groups, num_groups, group_names):
+    """The per-group classes' constructor arguments, checked -> (ids, G, names as a tuple of str or None)."""
+    ids = [int(g) for g in groups]
+    if not ids:
+        raise ValueError('groups: one id per env, got none')
+    G = max(ids) + 1 if num_groups is None else int(num_groups)
+    if not 1 <= G <= MAX_GROUPS:
+        raise ValueError('num_groups={} outside 1..{}'.format(G, MAX_GROUPS))
+    if min(ids) < 0 or max(ids) >= G:
+        raise ValueError('group ids must lie in 0..{}'.format(G - 1))
+    if group_names is not None and len(group_names) != G:
+        raise ValueError('group_names: {} names for {} groups'.format(len(group_names), G))
+    return ids, G, None if group_names is None else tuple(str(n) for n in group_names)
+
+
+def own_or_for_envs(option, cls, envs):
+    """An option of the train functions or of the agent -> None (falsy), the caller's own ``cls`` object, or
+    (anything else that is true) ``cls.for_envs(envs)``."""
+    if isinstance(option, cls):
+        return option
+    return cls.for_envs(envs) if option else None
+
+
 class ReturnNormalizer(object):
     """The state of the scaling (module docstring) and its launches.
 
@@ -158,20 +181,10 @@ class ReturnNormalizer(object):
     """
 
     def __init__(self, groups, num_groups=None, group_names=None, epsilon=1e-8, clip=10.0):
-        ids = [int(g) for g in groups]
-        if not ids:
-            raise ValueError('groups: one id per env, got none')
-        G = max(ids) + 1 if num_groups is None else int(num_groups)
-        if not 1 <= G <= MAX_GROUPS:
-            raise ValueError('num_groups={} outside 1..{}'.format(G, MAX_GROUPS))
-        if min(ids) < 0 or max(ids) >= G:
-            raise ValueError('group ids must lie in 0..{}'.format(G - 1))
-        if group_names is not None and len(group_names) != G:
-            raise ValueError('group_names: {} names for {} groups'.format(len(group_names), G))
+        ids, G, self.group_names = check_groups(groups, num_groups, group_names)
         if not float(epsilon) >= 0.0:
             raise ValueError('epsilon must not be negative, got {}'.format(epsilon))
         self.num_envs, self.num_groups = len(ids), G
-        self.group_names = None if group_names is None else tuple(str(n) for n in group_names)
         self.epsilon, self.clip = float(epsilon), float(clip)
         self.frozen = False
         self.groups = torch.tensor(ids, dtype=torch.uint8)

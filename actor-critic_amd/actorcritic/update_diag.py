@@ -30,7 +30,7 @@ import numpy as np
 import torch
 
 from actorcritic import _lib
-from actorcritic.return_norm import MAX_GROUPS, groups_for_envs
+from actorcritic.return_norm import check_groups, groups_for_envs
 
 VALUE_COLS = 6   # n, sum v, sum y, sum y^2, sum e, sum e^2
 POLICY_COLS = 4  # n, sum KL, sum H | max KL
@@ -210,20 +210,10 @@ class UpdateDiagnostics(object):
     """
 
     def __init__(self, groups, num_groups=None, group_names=None, forward_rows=1024):
-        ids = [int(g) for g in groups]
-        if not ids:
-            raise ValueError('groups: one id per env, got none')
-        G = max(ids) + 1 if num_groups is None else int(num_groups)
-        if not 1 <= G <= MAX_GROUPS:
-            raise ValueError('num_groups={} outside 1..{}'.format(G, MAX_GROUPS))
-        if min(ids) < 0 or max(ids) >= G:
-            raise ValueError('group ids must lie in 0..{}'.format(G - 1))
-        if group_names is not None and len(group_names) != G:
-            raise ValueError('group_names: {} names for {} groups'.format(len(group_names), G))
+        ids, G, self.group_names = check_groups(groups, num_groups, group_names)
         if int(forward_rows) < 1:
             raise ValueError('forward_rows must be at least 1, got {}'.format(forward_rows))
         self.num_envs, self.num_groups = len(ids), G
-        self.group_names = None if group_names is None else tuple(str(n) for n in group_names)
         self.forward_rows = int(forward_rows)
         self.groups = torch.tensor(ids, dtype=torch.uint8)
         self.armed = False

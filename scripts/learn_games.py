@@ -90,22 +90,19 @@ def run(args, seed, emit):
     for g in eval_games if start == 0 else ():  # (a resumed curve has its first lines already)
         emit(dict(head, policy='uniform', updates=0, env_steps=0, **tag(g),
                   **stats(evaluate(None, eval_envs(g), episodes(g), uniform=True, seed=seed))))
-    norm = False
-    if args.normalize_returns:  # built here and handed to the example, so that its scale can be logged
-        from actorcritic.envs.games.host import env_game_ids
-        from actorcritic.return_norm import ReturnNormalizer
-        norm = ReturnNormalizer(env_game_ids(args.game, N), num_groups=len(GAMES), group_names=GAMES)
-    ep_stats = None
-    if args.episode_stats:  # built here and handed to the example (no summary path: it never reads them)
-        from actorcritic.envs.games.host import env_game_ids
-        from actorcritic.episode_stats import EpisodeStats
-        ep_stats = EpisodeStats(env_game_ids(args.game, N), num_groups=len(GAMES), group_names=GAMES)
-    diag = None
+    norm, ep_stats, diag = False, None, None
     point = lambda u: u % args.every == 0 or u == args.updates
+    from actorcritic.envs.games.host import env_game_ids
+    groups = dict(groups=env_game_ids(args.game, N), num_groups=len(GAMES), group_names=GAMES)  # one per game
+    if args.normalize_returns:  # built here and handed to the example, so that its scale can be logged
+        from actorcritic.return_norm import ReturnNormalizer
+        norm = ReturnNormalizer(**groups)
+    if args.episode_stats:  # built here and handed to the example (no summary path: it never reads them)
+        from actorcritic.episode_stats import EpisodeStats
+        ep_stats = EpisodeStats(**groups)
     if args.diagnostics:  # built here and armed here, for the update that ends at a point (no summary path)
-        from actorcritic.envs.games.host import env_game_ids
         from actorcritic.update_diag import UpdateDiagnostics
-        diag = UpdateDiagnostics(env_game_ids(args.game, N), num_groups=len(GAMES), group_names=GAMES)
+        diag = UpdateDiagnostics(**groups)
         if point(start + 1):
             diag.request()
     t0 = time.perf_counter()
@@ -145,15 +142,13 @@ def run(args, seed, emit):
                           env_steps=updates * N * T, wall_s=round(train_s, 2), **tag(g), **inv,
                           **stats(play(model, g)), **train, **update_diag))
 
+    kwargs = dict(max_updates=args.updates - start, seed=seed, game=args.game, on_update=on_update,
+                  mask_actions=args.mask_actions, normalize_returns=norm, episode_stats=ep_stats,
+                  diagnostics=diag or False, **rules, **fused, **keep)
     if args.algo == 'ppo':
-        train_ppo(args.game, N, T, ckpt_dir, args.game, max_updates=args.updates - start, seed=seed, game=args.game,
-                  on_update=on_update, mask_actions=args.mask_actions, normalize_returns=norm,
-                  episode_stats=ep_stats, diagnostics=diag or False, **rules, **fused, **keep)
+        train_ppo(args.game, N, T, ckpt_dir, args.game, **kwargs)
     else:
-        train_a2c_acktr(args.algo == 'acktr', args.game, N, T, ckpt_dir, args.game, max_updates=args.updates - start,
-                        seed=seed, game=args.game, on_update=on_update, mask_actions=args.mask_actions,
-                        normalize_returns=norm, episode_stats=ep_stats, diagnostics=diag or False, **rules, **fused,
-                        **keep)
+        train_a2c_acktr(args.algo == 'acktr', args.game, N, T, ckpt_dir, args.game, **kwargs)
 
 
 def main():

@@ -448,6 +448,36 @@ def test_example_resumes_its_own_run(lib, cuda, tmp_path, monkeypatch):
         _train(cut, 1, **opts)
 
 
+def test_ppo_example_resumes_its_own_run(lib, cuda, tmp_path, monkeypatch):
+    """The straight-versus-cut core of the test above through train_ppo: the loop is the same one."""
+    from actorcritic import checkpoint
+    from actorcritic import session as sess
+    from actorcritic.examples.atari.ppo import train_ppo
+    _rollout_form(monkeypatch, True)
+    for var in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK'):
+        monkeypatch.delenv(var, raising=False)
+
+    def train(directory, max_updates):
+        sess.reset_default_graph()
+        return train_ppo('DeviceGame', 4, 3, str(directory), 'Run', max_updates=max_updates, seed=2,
+                         game='catch+breakout', num_epochs=2, num_minibatches=2, run_state=True, checkpoint_every=2,
+                         normalize_returns=True)
+
+    straight, cut = tmp_path / 'straight', tmp_path / 'cut'
+    straight.mkdir()
+    cut.mkdir()
+    train(straight, 4)
+    assert sorted(p.name for p in straight.iterdir()) == ['Run-2.pt', 'Run-2.run0.pt', 'Run-4.pt', 'Run-4.run0.pt',
+                                                          'checkpoint']
+    train(cut, 2)
+    assert sorted(p.name for p in cut.iterdir()) == ['Run-2.pt', 'Run-2.run0.pt', 'checkpoint']
+    train(cut, 2)  # resumes
+    assert checkpoint.latest(str(cut)) == str(cut / 'Run-4.pt')
+    assert checkpoint.latest(str(straight)) == str(straight / 'Run-4.pt')
+    for name in ('Run-4.pt', 'Run-4.run0.pt', 'Run-2.pt', 'Run-2.run0.pt'):
+        _assert_blobs_equal(_load(cut / name), _load(straight / name), name + ': ')
+
+
 # -- 8. two ranks -------------------------------------------------------------------------------
 WORLD = 2
 
