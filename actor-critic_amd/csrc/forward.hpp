@@ -7,6 +7,8 @@
 //
 // Part of net.hip's translation unit: it is included after the mode globals
 // (g_gemm_mode, g_forward_mode), prof_begin / prof_end, Layout and masks_ok that it uses.
+// dispatch_c3, by which every entry point of the translation unit picks its C3
+// instantiation, is defined here.
 #pragma once
 
 #include <algorithm>
@@ -20,6 +22,7 @@
 #include "games.hpp"
 #include "gemm.hpp"
 #include "gemm3.hpp"
+#include "prepview.hpp"
 #include "stepper.hpp"
 #include "tower.hpp"
 #include "towersplit.hpp"
@@ -575,7 +578,8 @@ static int forward_impl(const Layout& L, const float* P, const uint8_t* obs,
   int nz, chunk;
   fc4_plan(B, K4, &nz, &chunk);
   const bool split = nz > 1 && a->ws && a->ws_floats >= (long long)nz * (B + 1) * 512;
-  const char* w4p = prep ? static_cast<const char*>(prep) + TowerPrep<C3>::BYTES + CT2::BYTES : nullptr;
+  const PrepView<C3> pv{prep};
+  const char* w4p = pv.fc4();
   // the split rollout step's pending env states (Env::pend_area: after fc4's slabs in
   // the forward workspace, or the caller's buffer); only with the rollout fc4 kernel,
   // the one launch that commits them
@@ -589,9 +593,7 @@ static int forward_impl(const Layout& L, const float* P, const uint8_t* obs,
     // between fused steps left behind -- the flag is cleared on commit)
     const typename Env::Commit cm = Env::commit(tail, pend, B);
     if (!(fc4_roll &&
-          launch_fc4_roll(a->a3, st * K4, B, K4, w4p, nz, chunk, a->ws,
-                          reinterpret_cast<const unsigned*>(static_cast<const char*>(prep) + TowerPrep<C3>::HDR),
-                          s, cm))) {
+          launch_fc4_roll(a->a3, st * K4, B, K4, w4p, nz, chunk, a->ws, pv.hdr(), s, cm))) {
       // (no fused tower without the rollout fc4: no split step, nothing pending)
       EpiPartial epi{a->ws, B, 512};
       launch_mm<64, 128, 32, 1, 2, true, false, 16>(opA4, opB4, epi, B, 512, K4, nz, chunk, s);
@@ -638,6 +640,12 @@ static bool spans32(long long rows, long long stride, long long per_row) {
   return rows <= 0 || (rows - 1) * stride + per_row < (1LL << 31);
 }
 
+// f(std::integral_constant<int, C3>) for a layout's C3 (make_layout: 32 or 64)
+template <class F>
+static __forceinline__ auto dispatch_c3(int C3, F&& f) {
+  return C3 == 32 ? f(std::integral_constant<int, 32>{}) : f(std::integral_constant<int, 64>{});
+}
+
 template <class Env = SynthEnv>
 static int forward_dispatch(const acmi_net_t* net, const uint8_t* obs, int64_t img_stride,
                             int B, const acmi_acts_t* acts, int want_value,
@@ -658,11 +666,10 @@ static int forward_dispatch(const acmi_net_t* net, const uint8_t* obs, int64_t i
                ACMI_ERR_ARG, "acmi_forward: batch spans >= 2^31 elements (B=%d)", B);
   if (B == 0) return ACMI_OK;
   hipStream_t s = (hipStream_t)stream;
-  if (L.C3 == 32)
-    return forward_impl<32, Env>(L, net->params, obs, img_stride, B, acts, want_value, act_stride, s, tail,
-                                 net->conv_prep);
-  return forward_impl<64, Env>(L, net->params, obs, img_stride, B, acts, want_value, act_stride, s, tail,
-                               net->conv_prep);
+  return dispatch_c3(L.C3, [&](auto c3) {
+    return forward_impl<decltype(c3)::value, Env>(L, net->params, obs, img_stride, B, acts, want_value, act_stride, s,
+                                                  tail, net->conv_prep);
+  });
 }
 
 }  // namespace acmi

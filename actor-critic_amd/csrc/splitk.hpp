@@ -450,10 +450,7 @@ static WgradPlan wgrad_plan(int K, int cout, bool with_stats, long long rows, bo
     plan_rounds(rows, p.sp6.ngroups, kCUs, &p.nc, &p.ch, 2048);
   else if (p.six)  // one 512-thread block per CU (2 x 64 accumulators per wave)
     plan_rounds(rows, p.sp6.ngroups, kCUs, &p.nc, &p.ch);
-  else if (p.slabs && mode == ACMI_GEMM_X3)
-    plan_rounds(rows, p.sp.ngroups, kCUs * std::min(8, 160 * 1024 / symred3_lds_bytes()), &p.nc,
-                &p.ch);
-  else if (p.slabs)
+  else if (p.slabs)  // f32 slab groups (in x3 mode every slab plan that runs, K = 512 / 576, is a six-slab one)
     plan_rounds(rows, p.sp.ngroups, kCUs * std::min(8, 160 * 1024 / symred_lds_bytes<16>()), &p.nc,
                 &p.ch);
   else if (with_stats)
@@ -563,8 +560,6 @@ static int wgrad_layer(const Src& src, int K, long long rows, const float* dy,
   if constexpr (std::is_same<typename Src::elem_t, float>::value) {
     if (pl.six)  // six-slab groups, bf16x3 split operands (f16x2 with published bounds)
       launch_symred6(opB, epi, pl.sp6, I, J, (int)rows, nc, ch, s, pmax, ymax, kp);
-    else if (pl.slabs && mode == ACMI_GEMM_X3)  // slab groups, bf16x3 split operands
-      launch_symred3(opB, epi, pl.sp, I, J, (int)rows, nc, ch, s);
     else if (pl.slabs)  // slab groups over the upper triangle of P^T P and the dY columns
       launch_symred<16>(opB, epi, pl.sp, I, J, (int)rows, nc, ch, s);
     else if (with_stats)  // 128x128 live tiles (fc4: K not a multiple of 64)
@@ -660,7 +655,8 @@ static long long afactor_ws_floats(int B) { return conv1_afactor_ws_ints(400LL *
 //   backward:      [scratch kBandScratch | conv1 A-factor ints | partials ...]
 //   output stats:  [scratch kBandScratch | sampled head gradients B x ldg | partials ...]
 // (prefixes rounded to 256 B); the partial region is the rest of the caller's
-// buffer, at least bwd_partial_floats
+// buffer, at least bwd_partial_floats.  backward.hpp's BwdWs / StatsWs are the
+// views of the two layouts, by these prefix sizes.
 static long long head_grad_ldg(int A) { return roundup4(A + 1) < 8 ? 8 : roundup4(A + 1); }
 static long long bwd_prefix_floats(int B) { return kBandScratch + (afactor_ws_floats(B) + 63) / 64 * 64; }
 static long long stats_prefix_floats(int B, int A) { return kBandScratch + ((long long)B * head_grad_ldg(A) + 63) / 64 * 64; }

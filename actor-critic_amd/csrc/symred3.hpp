@@ -16,21 +16,20 @@
 // Rate: 6 x 32 cycles per 32x32x16 tile vs 8 x 64 for the same K on
 // v_mfma_f32_32x32x2_f32 (MI355X_MICROARCH.md constants table).
 //
-// Same slab plan (sym_plan), grid, staging loads, split-K partial layout and
-// column-sum contract as symred_kernel (symred.hpp), so finalize_wgrad_body is
-// shared.  What differs:
+// Same grid order, staging loads, split-K partial layout and column-sum contract
+// as symred_kernel (symred.hpp), so finalize_wgrad_body is shared.  What differs:
+//  * Six staged slabs per block (SymPlan6) instead of four; see below.
 //  * LDS image: per stage of BK = 16 k-rows, three parts (h, m, l), each
-//    [16 k][256 columns] of bf16 (512-byte rows) with 8-byte column slots
-//    XOR-swizzled by 8*(k & 3): the 16-byte commit stores (8 lanes of one
-//    k-row) and the ds_read_b64_tr_b16 transposed fragment reads (4 k-rows x 16
-//    columns per 16 lanes) are both bank-conflict free.  24 KB per stage, 48 KB
-//    double-buffered -> 3 blocks per CU.
+//    [16 k][384 columns] of bf16 (768-byte rows) with 8-byte column slots
+//    XOR-swizzled by 8*(k & 3): the commit stores and the ds_read_b64_tr_b16
+//    transposed fragment reads (4 k-rows x 16 columns per 16 lanes) are both
+//    bank-conflict free.  36 KB per stage, 72 KB double-buffered.
 //  * Fragments come from ds_read_b64_tr_b16 (cdna_hip_programming.md T10): two
 //    per 32-column block and part give lane l the 8 consecutive k of column
 //    l & 31 that the 32x32x16 operand map wants (A[r][8h + e], B[8h + e][r]).
 //  * Column sums (the homogeneous row) are summed in f32 from the staged
-//    values at the commit (each thread: its 8 columns over its k-rows), then
-//    reduced over the 8 k-row threads of a column through LDS at the end.
+//    values at the commit (each thread: its 12 columns over its k-rows), then
+//    reduced over the 16 k-row threads of a column through LDS at the end.
 #pragma once
 
 #include <stdlib.h>
@@ -47,177 +46,13 @@
 
 namespace acmi {
 
-constexpr int kX3Rows = 16;                 // k-rows per stage
-constexpr int kX3RowBytes = 512;            // 256 bf16 columns
-constexpr int kX3Part = kX3Rows * kX3RowBytes;
-constexpr int kX3Buf = 3 * kX3Part;         // h, m, l
-constexpr int symred3_lds_bytes() { return 2 * kX3Buf; }
-
-template <class Op, class Epi>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3)))
-void symred3_kernel(Op op, Epi epi, SymPlan plan, int I, int J, int K, int k_chunk) {
-  constexpr int BK = kX3Rows;
-  constexpr int NR = BK / 8;  // staging k-rows per thread (32 threads per k-row)
-  __shared__ __attribute__((aligned(16))) char lds[2 * kX3Buf];
-
-  const int total = gridDim.x;
-  const int b = blockIdx.x;
-  const int xcd = b & 7, base8 = total >> 3, rem = total & 7;
-  const int l = xcd * base8 + min(xcd, rem) + (b >> 3);
-  const int ng = plan.ngroups;
-  const int bz = l / ng;
-  const SymGroup& G = plan.g[l - bz * ng];
-  set_z(epi, bz);
-  const int kbeg = bz * k_chunk;
-  const int kend = min(K, kbeg + k_chunk);
-  const int nk = kend > kbeg ? (kend - kbeg + BK - 1) / BK : 0;
-
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = tid >> 6;
-
-  // staging: thread -> 8 consecutive staged columns (16-byte chunk c16 of a
-  // 512-byte LDS row) of k-rows tid/32 + 8*rr
-  const int c16 = tid & 31;
-  const int scol = c16 * 8;
-  const int sbase = G.base[scol >> 6];
-  const int jcol = sbase >= 0 ? sbase + (scol & 63) : J;  // >= J stages zeros
-  const typename Op::CB c0 = op.col_base(jcol), c1 = op.col_base(jcol + 4);
-  typename Op::St ra[NR][2];
-  float csum[8];
-#pragma unroll
-  for (int e = 0; e < 8; ++e) csum[e] = 0.f;
-  // rows kbeg + tid/32 + 8rr, advanced BK per fetch (fetches run in k order)
-  typename Op::It it[NR];
-#pragma unroll
-  for (int rr = 0; rr < NR; ++rr) it[rr] = op.iter(kbeg + (tid >> 5) + 8 * rr);
-
-  auto fetch = [&](int k0) {
-#pragma unroll
-    for (int rr = 0; rr < NR; ++rr) {
-      const int k = k0 + (tid >> 5) + 8 * rr;
-      ra[rr][0] = op.stage_it(it[rr], c0, k < kend);
-      ra[rr][1] = op.stage_it(it[rr], c1, k < kend);
-      op.template advance<BK>(it[rr]);
-    }
-  };
-  auto commit = [&](int buf) {
-    char* s = lds + buf * kX3Buf;
-#pragma unroll
-    for (int rr = 0; rr < NR; ++rr) {
-      const int k = (tid >> 5) + 8 * rr;
-      const float4 x0 = finish(ra[rr][0]);
-      const float4 x1 = finish(ra[rr][1]);
-      csum[0] += x0.x;
-      csum[1] += x0.y;
-      csum[2] += x0.z;
-      csum[3] += x0.w;
-      csum[4] += x1.x;
-      csum[5] += x1.y;
-      csum[6] += x1.z;
-      csum[7] += x1.w;
-      uint4 h, m, lo;
-      split3(x0.x, x0.y, h.x, m.x, lo.x);
-      split3(x0.z, x0.w, h.y, m.y, lo.y);
-      split3(x1.x, x1.y, h.z, m.z, lo.z);
-      split3(x1.z, x1.w, h.w, m.w, lo.w);
-      const int off = k * kX3RowBytes + 16 * (c16 ^ (4 * (k & 3)));
-      *reinterpret_cast<uint4*>(s + off) = h;
-      *reinterpret_cast<uint4*>(s + kX3Part + off) = m;
-      *reinterpret_cast<uint4*>(s + 2 * kX3Part + off) = lo;
-    }
-  };
-
-  const int sa = G.wa[wave], sb = G.wb[wave];
-  const bool idle = sa < 0;
-  const int ib = idle ? 0 : G.base[sa];  // row slabs are P slabs: column == row index
-  const int jb = idle ? 0 : G.base[sb];
-  const bool do_cs = !idle && ib == 0;
-  // transposed-read address of lane l inside a 32-column block: group g =
-  // (l>>4)&1 -> columns 16g.., lane 4q+p -> k-row 8h+q, columns 4p..4p+3 (one
-  // 8-byte slot), swizzled like the commit (8-byte slot ^ 8q)
-  const int q = (lane >> 2) & 3, p = lane & 3, g = (lane >> 4) & 1, kh = lane >> 5;
-  auto slot_off = [&](int colblock) {  // colblock: first staged column (multiple of 32)
-    const int slot = (colblock >> 2) + 4 * g + p;
-    return (8 * kh + q) * kX3RowBytes + 8 * (slot ^ (8 * q));
-  };
-  const int aoff0 = slot_off(64 * (idle ? 0 : sa)), aoff1 = slot_off(64 * (idle ? 0 : sa) + 32);
-  const int boff0 = slot_off(64 * (idle ? 0 : sb)), boff1 = slot_off(64 * (idle ? 0 : sb) + 32);
-
-  f32x16 acc[2][2];
-#pragma unroll
-  for (int x = 0; x < 2; ++x)
-#pragma unroll
-    for (int y = 0; y < 2; ++y)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[x][y][r] = 0.f;
-
-  if (nk > 0) {
-    fetch(kbeg);
-    commit(0);
-  }
-  __syncthreads();
-
-  auto step = [&](int kt, int cur, auto MF, auto NTc) {
-    constexpr bool mf = decltype(MF)::value;
-    constexpr int NT = decltype(NTc)::value;
-    fetch(kbeg + (kt + 1) * BK);
-    __builtin_amdgcn_sched_barrier(0);
-    if constexpr (mf) {
-      const char* s = lds + cur * kX3Buf;
-      bf16x8 a[2][3], bb[2][3];
-#pragma unroll
-      for (int pt = 0; pt < 3; ++pt) {
-        const char* sp = s + pt * kX3Part;
-        a[0][pt] = cat8(ds_tr16(sp + aoff0), ds_tr16(sp + aoff0 + 4 * kX3RowBytes));
-        a[1][pt] = cat8(ds_tr16(sp + aoff1), ds_tr16(sp + aoff1 + 4 * kX3RowBytes));
-        bb[0][pt] = cat8(ds_tr16(sp + boff0), ds_tr16(sp + boff0 + 4 * kX3RowBytes));
-        if constexpr (NT == 2)
-          bb[1][pt] = cat8(ds_tr16(sp + boff1), ds_tr16(sp + boff1 + 4 * kX3RowBytes));
-      }
-#pragma unroll
-      for (int tm = 0; tm < 2; ++tm)
-#pragma unroll
-        for (int tn = 0; tn < NT; ++tn) acc[tm][tn] = mfma_x3(a[tm], bb[tn], acc[tm][tn]);
-    }
-    __builtin_amdgcn_sched_barrier(0);
-    commit(cur ^ 1);
-    __syncthreads();
-  };
-  using T = std::integral_constant<bool, true>;
-  using F = std::integral_constant<bool, false>;
-  using N2 = std::integral_constant<int, 2>;
-  using N1 = std::integral_constant<int, 1>;
-  const bool half = jb + 32 >= J;
-  if (idle) {
-    for (int kt = 0; kt < nk; ++kt) step(kt, kt & 1, F{}, N2{});
-  } else if (half) {
-    for (int kt = 0; kt < nk; ++kt) step(kt, kt & 1, T{}, N1{});
-  } else {
-    for (int kt = 0; kt < nk; ++kt) step(kt, kt & 1, T{}, N2{});
-  }
-
-  // column sums: [8 k-row threads][256 columns] through the (now free) LDS
-  float* cs = reinterpret_cast<float*>(lds);
-#pragma unroll
-  for (int e = 0; e < 8; ++e) cs[(tid >> 5) * 256 + scol + e] = csum[e];
-  __syncthreads();
-  if (idle) return;
-  store_tile<2, 2>(epi, acc, ib, jb, lane, I, J);
-  if (do_cs) {
-    const int col = 64 * sb + lane;
-    float t = 0.f;
-#pragma unroll
-    for (int r = 0; r < 8; ++r) t += cs[r * 256 + col];
-    if (jb + lane < J) epi.colsum(jb + lane, t);
-  }
-}
+constexpr int kX3Rows = 16;  // k-rows per stage
 
 // ---------------------------------------------------------------------------
 // Six-slab groups: 8 waves (512 threads), two 64x64 sub-tiles per wave, six
-// staged slabs (384 columns) per block.  The no-MFMA probe of symred3_kernel
-// (ACMI_SYMRED=m: 0.87 of 1.50 ms at conv2's shape) shows the staging gather
-// alone is as long as the MFMA work: with one sub-tile per staged slab the
+// staged slabs (384 columns) per block.  The no-MFMA probe of the four-slab
+// bf16x3 kernel this replaced (0.87 of 1.50 ms at conv2's shape) showed the staging
+// gather alone as long as the MFMA work: with one sub-tile per staged slab the
 // loads would need ~10 TB/s from L2 to keep the matrix cores busy.  Covering
 // the needed sub-tiles with 6-slab groups of <= 16 sub-tiles takes 3 groups
 // for conv2 / the heads (8 P slabs + dY; 11 groups of 4 slabs before) and 4
@@ -226,7 +61,10 @@ void symred3_kernel(Op op, Epi epi, SymPlan plan, int I, int J, int K, int k_chu
 // The slab sets are fixed coverings of the slab pairs (found offline by a
 // local search over 6-subsets: every pair of slabs, the dY slab included, lies
 // in some set); sym_plan6 assigns the sub-tiles to them by bipartite matching
-// with a balanced per-group capacity.
+// with a balanced per-group capacity.  Measured at the bench shape (conv2 patch
+// rows, M = 10240): six slabs 1.27 ms, without the two-ahead loads 1.36, four
+// slabs 1.52 (that kernel is removed: sym_plan6 covers every shape sym_plan does
+// in x3 mode, K = 512 and 576).
 // ---------------------------------------------------------------------------
 constexpr int kSixSlabs = 6;
 constexpr int kSixRowBytes = kSixSlabs * 64 * 2;      // 768
@@ -682,18 +520,6 @@ inline void launch_symred6(const Op& op, const Epi& e, const SymPlan6& plan, int
   else
     hipLaunchKernelGGL((symred6_kernel<Op, Epi, true>), dim3(plan.ngroups * nchunk), dim3(512), 0, s, op, e,
                        plan, I, J, K, k_chunk, nullptr, nullptr, 0);
-}
-
-// Six-slab groups (symred6_kernel, loads two K-tiles ahead) where sym_plan6 has
-// a covering, else four-slab groups (symred3_kernel).  Measured at the bench
-// shape (conv2 patch rows, M = 10240): six 1.27 ms, six without the two-ahead
-// loads 1.36, four 1.52, four with interleaved tiles 1.50; timing probes of the
-// four-slab kernel without the operand split 1.43, without MFMAs 0.87.
-template <class Op, class Epi>
-inline void launch_symred3(const Op& op, const Epi& e, const SymPlan& plan, int I, int J, int K,
-                           int nchunk, int k_chunk, hipStream_t s) {
-  hipLaunchKernelGGL((symred3_kernel<Op, Epi>), dim3(plan.ngroups * nchunk), dim3(256), 0, s, op, e, plan, I, J,
-                     K, k_chunk);
 }
 
 }  // namespace acmi

@@ -1,9 +1,10 @@
 """Kernel paths that only engage at larger batches, and full-size properties.
 
 The GEMM launches pick tiles, split-K chunkings and fused reductions by batch size
-(net.hip: 128-row conv1 / 64x64 conv2 tiles and split-K fc4 below 2048 images,
-256-row tiles above; plan_rounds chunk counts; the i8 conv1 A factor's chunks;
-the heads kernel's NZ-way slab reduce; the narrow Gram kernel).  These tests run
+(net.hip's translation unit -- forward.hpp: 128-row conv1 / 64x64 conv2 tiles and
+split-K fc4 below 2048 images, 256-row tiles above, the heads kernel's NZ-way slab
+reduce; splitk.hpp / backward.hpp: plan_rounds chunk counts, the i8 conv1 A factor's
+chunks, the narrow Gram kernel).  These tests run
 each regime against float64 PyTorch references, and check at the BASELINE.json
 workload size (512 envs x 20 steps) the size-independent properties the domain
 offers: bit-identical replays (no atomics anywhere in the update) and symmetric A

@@ -42,7 +42,7 @@ What the cases found (measured on the parent of the commit that added them, SEED
     factor was off by 2.3e-4 (conv2*2^6-catch) .. 5.5e-3 (fc4*2^6-random) of its range,
     and 1.0 .. 1.2 (all of it) in conv3*2^6-catch / -random and fc4*2^6-catch, bound 5e-5
     (those cases and conv1*2^6-random, saturating-conv1*2^6 failed).  Fixed in
-    csrc/net.hip: -(the other actions' sum) / se where the others hold less than 2^-7
+    csrc/backward.hpp: -(the other actions' sum) / se where the others hold less than 2^-7
     of the sum (elsewhere the subtraction is within 2^-17 of the column and stays, so
     unsaturated runs reproduce bit for bit); oracle.sampled_head_grads takes that form
     on every row.
