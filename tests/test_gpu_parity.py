@@ -291,6 +291,18 @@ def test_first_order_optimizers_match_oracle(lib, cuda):
     rp, rms, rmom = oracle.rmsprop_apply(p.astype(np.float64), np.ones(n), np.zeros(n), g.astype(np.float64), 7e-4,
                                          0.5)
     np.testing.assert_allclose(P.cpu().numpy(), rp, rtol=1e-6, atol=1e-7)
+    assert norm.item() == pytest.approx(np.linalg.norm(g.astype(np.float64)), rel=1e-5)
+    np.testing.assert_allclose(mom.cpu().numpy(), rmom, rtol=1e-5, atol=1e-11)
+    # ms through its gradient term: the clipped gradients leave ms within 4.8e-6 of
+    # decay * 1, so a relative comparison of ms itself (rtol = 1e-5 before) was met by
+    # ms = decay * ms.  ms - decay ms_old against (1 - decay) g^2 sc^2, within the 7
+    # float32 roundings of the path on decay ms_old + the term (3.8e-7; the largest
+    # terms are 12 times that)
+    decay = float(np.float32(0.9))
+    term = (1.0 - decay) * (g.astype(np.float64) * oracle.clip_scale(g.astype(np.float64), 0.5)[0]) ** 2
+    bound = 7 * 2.0 ** -24 * (decay + term)
+    assert term.max() > 10 * bound.max()
+    assert (np.abs((ms.cpu().numpy().astype(np.float64) - decay) - term) <= bound).all()
     np.testing.assert_allclose(ms.cpu().numpy(), rms, rtol=1e-5)
 
 
