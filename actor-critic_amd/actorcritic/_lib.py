@@ -209,6 +209,7 @@ _SIGS = {
                                  c_i64, c_vp]),
     'acmi_atari_rollout_frames': (c_int, [c_vp, c_i64, c_i64, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_i64,
                                           c_vp, c_i64, c_vp, c_vp]),
+    'acmi_atari_plan': (c_int, [c_int, c_int, ctypes.POINTER(ctypes.c_int32)]),
     'acmi_stream_wait_backward_dx': (c_int, [c_vp]),
     'acmi_selftest_plans': (c_int, [c_int]),
     'acmi_gemm_f32': (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_vp]),

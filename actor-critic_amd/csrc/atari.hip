@@ -207,30 +207,50 @@ __global__ __launch_bounds__(kAtariThreads) void atari_frames_kernel(
   }
 }
 
+// Launch planning of both launchers (host only): the shapes they take, the scales, the
+// kernel form and the LDS a workgroup gets.
+struct AtariPlan {
+  double sy, sx;
+  int max_run_y, max_run_x;
+  bool fixed3;      // runs of at most 3 source rows / columns (210x160): the <3,3> kernels
+  int band_rows;    // gray rows of the LDS band
+  size_t lds_frames, lds_rollout;
+};
+
+bool atari_plan(int H, int W, AtariPlan* p) {
+  // cv2 takes its integer-ratio fast path when both ratios are integers: not restated here
+  const bool int_ratio = H % kOut == 0 && W % kOut == 0;
+  if (!(H >= kOut && W >= kOut && H <= 6 * kOut && W <= 6 * kOut && W % 4 == 0 && H * W <= 40960 && !int_ratio))
+    return false;
+  p->sy = 1.0 / ((double)kOut / H);
+  p->sx = 1.0 / ((double)kOut / W);
+  p->max_run_y = area_max_run(H);
+  p->max_run_x = area_max_run(W);
+  p->fixed3 = p->max_run_y <= 3 && p->max_run_x <= 3;
+  // a band's source rows: at most kBandRows * scale + 2 of them
+  p->band_rows = std::min(H, (int)(kBandRows * p->sy) + 3);
+  const size_t tables = (kBandRows + kOut) * sizeof(AreaRun);
+  p->lds_frames = tables + (size_t)p->band_rows * W;
+  p->lds_rollout = tables + kBandRows * kOut + (size_t)p->band_rows * W;  // + rpix
+  return true;
+}
+
 int atari_launch(const char* what, const uint8_t* raw, int64_t env_stride, int64_t frame_stride,
                  const uint8_t* nframes, int N, int H, int W, int mode, const uint8_t* terminals,
                  const uint8_t* stack_in, uint8_t* out, int64_t out_stride, hipStream_t s) {
   const bool aligned = ((uintptr_t)raw % 4 == 0) && env_stride % 4 == 0 && frame_stride % 4 == 0 &&
                        (mode == 0 || ((uintptr_t)out % 4 == 0 && out_stride % 4 == 0 &&
                                       (mode != 1 || (uintptr_t)stack_in % 4 == 0)));
-  // cv2 takes its integer-ratio fast path when both ratios are integers: not restated here
-  const bool int_ratio = H % kOut == 0 && W % kOut == 0;
-  ACMI_REQUIRE(raw && out && N >= 0 && H >= kOut && W >= kOut && H <= 6 * kOut && W <= 6 * kOut &&
-                   W % 4 == 0 && H * W <= 40960 && !int_ratio && aligned &&
+  AtariPlan plan;
+  ACMI_REQUIRE(raw && out && N >= 0 && atari_plan(H, W, &plan) && aligned &&
                    (mode != 1 || stack_in) && frame_stride >= 0 &&
                    out_stride >= (mode == 0 ? kOut * kOut : 4 * kOut * kOut),
                ACMI_ERR_ARG, "%s: bad arguments", what);
   if (N == 0) return ACMI_OK;
-  const double sy = 1.0 / ((double)kOut / H), sx = 1.0 / ((double)kOut / W);
-  // a band's source rows: at most kBandRows * scale + 2 of them
-  const int band_rows = std::min(H, (int)(kBandRows * sy) + 3);
-  const size_t lds = (kBandRows + kOut) * sizeof(AreaRun) + (size_t)band_rows * W;
-  // 210x160: runs of at most 3 source rows / columns -> fixed 3x3 products per pixel
-  const bool fixed3 = area_max_run(H) <= 3 && area_max_run(W) <= 3;
-  auto kern = fixed3 ? atari_frames_kernel<3, 3> : atari_frames_kernel<0, 0>;
-  hipLaunchKernelGGL(kern, dim3(kBands, N), dim3(kAtariThreads), lds, s, raw, (long long)env_stride,
-                     (long long)frame_stride, nframes, H, W, sy, sx, mode, terminals, stack_in, out,
-                     (long long)out_stride);
+  auto kern = plan.fixed3 ? atari_frames_kernel<3, 3> : atari_frames_kernel<0, 0>;
+  hipLaunchKernelGGL(kern, dim3(kBands, N), dim3(kAtariThreads), plan.lds_frames, s, raw,
+                     (long long)env_stride, (long long)frame_stride, nframes, H, W, plan.sy, plan.sx, mode,
+                     terminals, stack_in, out, (long long)out_stride);
   ACMI_LAUNCH_CHECK(what);
   return ACMI_OK;
 }
@@ -394,9 +414,8 @@ int acmi_atari_rollout_frames(const uint8_t* frames, int64_t frame_stride, int64
                               acmi_stream_t stream) {
   using namespace acmi;
   constexpr int64_t kStack = 4 * kOut * kOut;
-  const bool int_ratio = H % kOut == 0 && W % kOut == 0;
-  const bool shape_ok = H >= kOut && W >= kOut && H <= 6 * kOut && W <= 6 * kOut && W % 4 == 0 &&
-                        H * W <= 40960 && !int_ratio;
+  AtariPlan plan;
+  const bool shape_ok = atari_plan(H, W, &plan);
   const bool frames_ok = frames && (uintptr_t)frames % 4 == 0 && frame_stride % 4 == 0 && nslots >= 0 &&
                          (!shape_ok || frame_stride >= (int64_t)H * W * 3);
   const bool out_ok = stack_out && (uintptr_t)stack_out % 4 == 0 && out_stride % 4 == 0 && out_stride >= kStack;
@@ -405,15 +424,25 @@ int acmi_atari_rollout_frames(const uint8_t* frames, int64_t frame_stride, int64
   ACMI_REQUIRE(shape_ok && frames_ok && out_ok && in_ok && N >= 0 && N <= 65535 && step_slot && reset_slot,
                ACMI_ERR_ARG, "acmi_atari_rollout_frames: bad arguments");
   if (N == 0) return ACMI_OK;
-  const double sy = 1.0 / ((double)kOut / H), sx = 1.0 / ((double)kOut / W);
-  const int band_rows = std::min(H, (int)(kBandRows * sy) + 3);
-  const size_t lds = (kBandRows + kOut) * sizeof(AreaRun) + kBandRows * kOut + (size_t)band_rows * W;
-  const bool fixed3 = area_max_run(H) <= 3 && area_max_run(W) <= 3;
-  auto kern = fixed3 ? atari_rollout_kernel<3, 3> : atari_rollout_kernel<0, 0>;
-  hipLaunchKernelGGL(kern, dim3(kBands, N), dim3(kAtariThreads), lds, (hipStream_t)stream, frames,
-                     (long long)frame_stride, (long long)nslots, H, W, sy, sx, step_slot, reset_slot,
-                     terminals, stack_in, (long long)in_stride, stack_out, (long long)out_stride, bad_envs);
+  auto kern = plan.fixed3 ? atari_rollout_kernel<3, 3> : atari_rollout_kernel<0, 0>;
+  hipLaunchKernelGGL(kern, dim3(kBands, N), dim3(kAtariThreads), plan.lds_rollout, (hipStream_t)stream,
+                     frames, (long long)frame_stride, (long long)nslots, H, W, plan.sy, plan.sx, step_slot,
+                     reset_slot, terminals, stack_in, (long long)in_stride, stack_out, (long long)out_stride,
+                     bad_envs);
   ACMI_LAUNCH_CHECK("acmi_atari_rollout_frames");
+  return ACMI_OK;
+}
+
+int acmi_atari_plan(int H, int W, int32_t out[6]) {
+  using namespace acmi;
+  AtariPlan plan;
+  ACMI_REQUIRE(out && atari_plan(H, W, &plan), ACMI_ERR_ARG, "acmi_atari_plan: bad arguments");
+  out[0] = plan.fixed3;
+  out[1] = plan.max_run_y;
+  out[2] = plan.max_run_x;
+  out[3] = plan.band_rows;
+  out[4] = (int32_t)plan.lds_frames;
+  out[5] = (int32_t)plan.lds_rollout;
   return ACMI_OK;
 }
 

@@ -867,6 +867,15 @@ int acmi_atari_rollout_frames(const uint8_t* frames, int64_t frame_stride,
                               int64_t in_stride, uint8_t* stack_out,
                               int64_t out_stride, int32_t* bad_envs,
                               acmi_stream_t stream);
+/* The launch plan the three entry points above make for H x W frames, host
+ * arithmetic only (no GPU needed, nothing launched): out = {fixed3, max_run_y,
+ * max_run_x, band_rows, lds_bytes_frames, lds_bytes_rollout} -- whether the
+ * kernels with run lengths fixed at 3 are chosen (both longest runs <= 3;
+ * otherwise the table-driven ones), the longest INTER_AREA run over the 84
+ * destination rows / columns, the gray source rows a band of 21 output rows
+ * may stage in LDS, and the dynamic LDS bytes of acmi_atari_preprocess / _stack
+ * and of acmi_atari_rollout_frames.  ACMI_ERR_ARG for a shape they refuse. */
+int acmi_atari_plan(int H, int W, int32_t out[6]);
 
 /* Rollout variant of acmi_forward: batch row b reads image b of `obs` and
  * writes activation row b*act_img_stride (env-major [N][T] buffers, the

@@ -88,7 +88,8 @@ def test_gray_restatement_matches_cv2_published_values():
 
 
 def test_area_tables_and_resize_restatement():
-    for ssize in (210, 160, 250, 100):
+    # (with the sides of tests/atari_frame_cases.py: scale 1.0, an integer ratio, runs of 7)
+    for ssize in (210, 160, 250, 100, 84, 88, 92, 168, 256, 320, 484, 487):
         runs = oracle.area_tables(ssize)
         assert len(runs) == 84
         for first, alphas in runs:
@@ -125,6 +126,50 @@ def test_frame_entry_points_reject_bad_shapes(lib):
     assert lib.acmi_atari_preprocess(buf, 80 * 160 * 3, 0, None, 1, 80, 160, out, 84 * 84, None) == -1
     assert lib.acmi_atari_stack(buf, 210 * 160 * 3, 0, None, 1, 210, 160, None, 0, None, out, 4 * 84 * 84,
                                 None) == -1  # step without a stack_in
+    # every call below is valid but for the argument named; host buffers, nothing launches
+    # (N = 0 with the same arguments is accepted, so the refusals are about that argument)
+    H, W, FRAME, GRAY, STACK = 210, 160, 210 * 160 * 3, 84 * 84, 4 * 84 * 84
+    big = ctypes.create_string_buffer(510 * 84 * 3 + 16)
+    stack = ctypes.create_string_buffer(2 * STACK + 16)
+    raw, sp = ctypes.addressof(big), ctypes.addressof(stack)
+    assert raw % 4 == 0 and sp % 4 == 0
+
+    def pre(H=H, W=W, raw=raw, stride=None, out_stride=GRAY, N=1):
+        return lib.acmi_atari_preprocess(raw, H * W * 3 if stride is None else stride, 0, None, N, H, W, sp,
+                                         out_stride, None)
+
+    def stk(H=H, W=W, raw=raw, stack_stride=STACK, stack_in=sp, stack_out=sp + STACK, N=1):
+        return lib.acmi_atari_stack(raw, H * W * 3, 0, None, N, H, W, None, 0, stack_in, stack_out, stack_stride, None)
+
+    assert pre(N=0) == 0 and stk(N=0) == 0
+    assert pre(W=162) == -1 and stk(W=162) == -1          # W % 4 != 0
+    assert pre(H=260) == -1 and stk(H=260) == -1          # 260 * 160 = 41600 > 40960
+    assert pre(H=256, N=0) == 0                           # (the bound itself is accepted)
+    # a side above 6 * 84 = 504.  With the other side at its minimum of 84 the area is
+    # already 505 * 84 = 42420 > 40960, so no shape reaches the 6 * 84 check alone; 508x84
+    # (no integer ratio, W % 4 == 0) is the nearest there is, and 84x508 the other way
+    assert pre(H=508, W=84) == -1 and pre(H=84, W=508) == -1 and stk(H=508, W=84) == -1
+    assert pre(raw=raw + 2) == -1 and stk(raw=raw + 2) == -1    # misaligned raw
+    assert pre(stride=FRAME + 2) == -1                          # misaligned env stride
+    assert pre(out_stride=GRAY - 1) == -1 and stk(stack_stride=STACK - 4) == -1  # outputs would overlap
+    assert stk(stack_out=sp + STACK + 2) == -1 and stk(stack_in=sp + 2) == -1    # misaligned stacks
+    assert b'acmi_atari_stack' in lib.acmi_last_error()
+
+    # the rollout entry point
+    slots = (ctypes.c_int32 * 2)(0, -1)
+    sl = ctypes.addressof(slots)
+
+    def roll(N=1, frame_stride=FRAME, stack_in=sp, in_stride=STACK, stack_out=sp + STACK, out_stride=STACK, W=W):
+        return lib.acmi_atari_rollout_frames(raw, frame_stride, 1, H, W, N, sl, sl + 4, None, stack_in, in_stride,
+                                             stack_out, out_stride, None, None)
+
+    assert roll(N=0) == 0
+    assert roll(N=65536) == -1                              # N > 65535 (the grid's y extent)
+    assert roll(frame_stride=FRAME - 4) == -1               # frame_stride < H*W*3
+    assert roll(N=0, stack_out=sp, in_stride=STACK, out_stride=STACK) == 0      # in place: one stride
+    assert roll(stack_out=sp, in_stride=STACK, out_stride=2 * STACK) == -1      # in place with two strides
+    assert roll(W=162, frame_stride=H * 162 * 3) == -1
+    assert b'acmi_atari_rollout_frames' in lib.acmi_last_error()
 
 
 # ---------------------------------------------------------------------------

@@ -47,13 +47,16 @@ def _expected(stack, G, R, term):
     return oracle.atari_stack(stack, G, terminal=term)
 
 
-# (has step frame, has reset frame, terminal flag): every row of the table, the
-# terminal flag both ways (it only matters where the env stepped)
-CASES = [(True, False, 0), (True, False, 1), (True, True, 0), (True, True, 1), (False, True, 0), (False, True, 1),
-         (False, False, 1)]
+# (has step frame, has reset frame, terminal flag): every row of the table, shared with
+# tests/test_gpu_atari_shapes.py, which runs them at every shape of atari_frame_cases.SHAPES
+from atari_frame_cases import CASES  # noqa: E402
 
 
-@pytest.fixture(scope='module', params=[(210, 160), (100, 92)], ids=['210x160-fixed3x3', '100x92-generic'])
+# 100x92 has runs of at most 3 in both directions, like 210x160: both take the kernel with
+# run lengths fixed at 3; 250x160 (y runs of 4) takes the table-driven one
+# (tests/test_atari_frame_cases_host.py proves it through acmi_atari_plan)
+@pytest.fixture(scope='module', params=[(210, 160), (100, 92), (250, 160)],
+                ids=['210x160-fixed3x3', '100x92-fixed3x3', '250x160-generic'])
 def kernel_case(request):
     """Five random frames spread over nslots = 2N slots, their oracle gray frames, and
     the per-env cases (which env gets which row is drawn)."""
@@ -173,19 +176,19 @@ def test_rollout_frames_slot_guard(lib, cuda, kernel_case):
 # ---------------------------------------------------------------------------
 # the rollout
 # ---------------------------------------------------------------------------
-def _ale(seed, A):
+def _ale(seed, A, shape=(210, 160)):
     from actorcritic import spaces
 
     class ALE(oracle.FakeALE):
         action_space = spaces.Discrete(A)
-        observation_space = spaces.Box(low=0, high=255, shape=(210, 160, 3), dtype=np.uint8)
+        observation_space = spaces.Box(low=0, high=255, shape=tuple(shape) + (3,), dtype=np.uint8)
 
-    return ALE(seed)
+    return ALE(seed, height=shape[0], width=shape[1])
 
 
-def _raw_chain(seed, A):
+def _raw_chain(seed, A, shape=(210, 160)):
     from actorcritic.envs.atari import wrappers
-    return wrappers.wrap_atari_env(_ale(seed, A), preprocess=False)
+    return wrappers.wrap_atari_env(_ale(seed, A, shape), preprocess=False)
 
 
 _GRAY = {}
@@ -199,7 +202,7 @@ def _oracle_gray(frame):
     return _GRAY[key]
 
 
-def _reference_envs(N, A):
+def _reference_envs(N, A, shape=(210, 160)):
     """The reference composition over an identical host chain, frames through the oracle."""
     from actorcritic import spaces
     from actorcritic.envs.atari import wrappers
@@ -213,7 +216,7 @@ def _reference_envs(N, A):
         def observation(self, frame):
             return _oracle_gray(np.ascontiguousarray(frame))
 
-    return [_AutoResetWrapper(wrappers.FrameStackWrapper(OraclePreprocess(_raw_chain(100 + i, A)), 4))
+    return [_AutoResetWrapper(wrappers.FrameStackWrapper(OraclePreprocess(_raw_chain(100 + i, A, shape)), 4))
             for i in range(N)]
 
 
@@ -221,8 +224,8 @@ class _Replay(object):
     """Replays returned actions through the reference envs and compares every output of
     interact() bit for bit; counts what the run contained."""
 
-    def __init__(self, N, A):
-        self.envs = _reference_envs(N, A)
+    def __init__(self, N, A, shape=(210, 160)):
+        self.envs = _reference_envs(N, A, shape)
         self.obs = [np.array(e.reset()) for e in self.envs]
         self.terminals = self.resets = self.both = 0
         self.prev = [False] * N
@@ -250,19 +253,38 @@ class _Replay(object):
             assert np.array_equal(nxt[n], self.obs[n]), ('next observation', n)
 
 
-def _host_agent(N, T, A, C3=32, copy_batches=False):
+def _host_agent(N, T, A, C3=32, copy_batches=False, shape=(210, 160)):
     from actorcritic import session as sess
     from actorcritic.agents import MultiEnvAgent
     from actorcritic.envs.atari.model import AtariModel
     from actorcritic.envs.atari.wrappers import HostAtariEnvs
     from actorcritic.multi_env import MultiEnv
     sess.reset_default_graph()
-    env = MultiEnv(HostAtariEnvs([_raw_chain(100 + i, A) for i in range(N)]))
+    env = MultiEnv(HostAtariEnvs([_raw_chain(100 + i, A, shape) for i in range(N)], height=shape[0],
+                                 width=shape[1]))
     assert env.batched is not None and env.num_envs == N and env.action_space.n == A
     assert tuple(env.observation_space.shape) == (84, 84, 4)
     params = oracle.init_params(A, C3, seed=1)
     model = AtariModel(env.observation_space, env.action_space, C3, params=params, random_seed=3)
     return env, model, MultiEnvAgent(env, model, T, copy_batches=copy_batches), params
+
+
+def _replay_rollouts(shape):
+    from actorcritic import session as sess
+    N, T, A = 9, 5, 4
+    env, model, agent, _ = _host_agent(N, T, A, shape=shape)
+    replay = _Replay(N, A, shape)
+    try:
+        with sess.Session() as s:
+            for _ in range(3):
+                data = agent.interact(s)
+                assert model.engine.lookup_rollout(data[0]) is not None
+                replay.check(data)
+    finally:
+        env.close()
+    print('host rollout {}x{}: {} terminals, {} resets, {} reset-and-terminal steps'.format(
+        shape[0], shape[1], replay.terminals, replay.resets, replay.both))
+    assert replay.terminals >= 1 and replay.resets >= 1 and replay.both >= 1
 
 
 def test_host_rollout_replays_through_the_reference_chain(lib, cuda):
@@ -272,21 +294,14 @@ def test_host_rollout_replays_through_the_reference_chain(lib, cuda):
     interesting steps; the counts depend on the GPU's draws (with random_seed=3 and
     init_params seed 1 they were 29 terminals, 28 resets and 6 reset-and-terminal steps
     in 135 env-steps)."""
-    from actorcritic import session as sess
-    N, T, A = 9, 5, 4
-    env, model, agent, _ = _host_agent(N, T, A)
-    replay = _Replay(N, A)
-    try:
-        with sess.Session() as s:
-            for _ in range(3):
-                data = agent.interact(s)
-                assert model.engine.lookup_rollout(data[0]) is not None
-                replay.check(data)
-    finally:
-        env.close()
-    print('host rollout: {} terminals, {} resets, {} reset-and-terminal steps'.format(
-        replay.terminals, replay.resets, replay.both))
-    assert replay.terminals >= 1 and replay.resets >= 1 and replay.both >= 1
+    _replay_rollouts((210, 160))
+
+
+def test_host_rollout_replays_at_a_generic_shape(lib, cuda):
+    """The same N, T and call count at 100x320, whose x runs of 5 take the table-driven
+    rollout kernel (FakeALE's terminals and rewards do not depend on the frame shape; the
+    actions drawn do)."""
+    _replay_rollouts((100, 320))
 
 
 def test_host_rollout_sampler_and_forward_consistency(lib, cuda):

@@ -52,6 +52,7 @@ def _call(lib, **kw):
     dict(in_stride=STACK - 4),
     dict(nslots=-1),
     dict(N=-1),
+    dict(N=65536),                                   # above the grid's y extent
     dict(frames=None),
     dict(stack_out=None),
     dict(step_slot=None),
