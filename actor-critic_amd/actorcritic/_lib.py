@@ -124,6 +124,10 @@ _SIGS = {
     # the same + truncated [N][T] u8 after terminals
     'acmi_returns_trunc': (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp]),
     'acmi_gae_trunc': (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_float, c_float, c_vp, c_vp, c_vp]),
+    # V-trace: (logits, ld, A, actions, behaviour_logp, rewards, terminals, truncated nullable, values, v_boot,
+    # N, T, gamma, lambda, rho_bar, c_bar, legal nullable, bad_rows nullable, targets, adv, rho, log_prob nullable)
+    'acmi_vtrace': (c_int, [c_vp, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_float,
+                            c_float, c_float, c_float, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     'acmi_adv_moments_ws_doubles': (c_i64, [c_i64]),
     'acmi_adv_moments': (c_int, [c_vp, c_i64, c_vp, c_vp, c_vp]),
     'acmi_adv_normalize': (c_int, [c_vp, c_i64, c_vp, ctypes.c_double, ctypes.c_double, c_vp]),

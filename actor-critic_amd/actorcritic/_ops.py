@@ -50,6 +50,14 @@ def targets(rewards, terminals, values, v_boot, N, T, gamma, gae_lambda, tables,
           (_p(values), _p(v_boot), N, T) + form + (_p(targets), _p(adv), stream))
 
 
+def vtrace(logits, ld, A, actions, behaviour_logp, rewards, terminals, values, v_boot, N, T, gamma, gae_lambda,
+           rho_bar, c_bar, targets, adv, rho, stream, truncated=None, legal=None, bad_rows=None, log_prob=None):
+    """acmi_vtrace: one entry point, the optional pointers are its nullable arguments."""
+    _lib.call('acmi_vtrace', _p(logits), ld, A, _p(actions), _p(behaviour_logp), _p(rewards), _p(terminals),
+              _p(truncated), _p(values), _p(v_boot), N, T, gamma, gae_lambda, rho_bar, c_bar, _p(legal),
+              _p(bad_rows), _p(targets), _p(adv), _p(rho), _p(log_prob), stream)
+
+
 def a2c_loss(logits, ld, values, actions, targets, adv, M, A, beta, vcoef, grad_scale, dhead, ldh, ws, loss_out,
              stream, legal=None, bad_rows=None):
     _call('acmi_a2c_loss', 'acmi_a2c_loss_masked',

@@ -24,6 +24,7 @@ class ActorCriticModel(object, metaclass=ABCMeta):
         self._rewards_placeholder = None
         self._terminals_placeholder = None
         self._truncations_placeholder = None
+        self._behaviour_log_probs_placeholder = None
 
         self._setup_placeholders(observation_space, action_space)
 
@@ -60,6 +61,14 @@ class ActorCriticModel(object, metaclass=ABCMeta):
         return self._truncations_placeholder
 
     @property
+    def behaviour_log_probs_placeholder(self):
+        """Optional, beyond the reference's five: float32 [env, step], the log-probability that the policy
+        which acted gave the taken action.  Read by :class:`actorcritic.objectives.VTraceObjective` alone.
+        Unfed, the behaviour policy is the batch's own forward -- with the rollout's cached activations the
+        policy that acted (the rule of PPO's old log-probabilities)."""
+        return self._behaviour_log_probs_placeholder
+
+    @property
     def policy(self):
         return self._policy
 
@@ -79,6 +88,7 @@ class ActorCriticModel(object, metaclass=ABCMeta):
         self._rewards_placeholder = Placeholder(np.float32, [None, None], 'rewards')
         self._terminals_placeholder = Placeholder(np.bool_, [None, None], 'terminals')
         self._truncations_placeholder = Placeholder(np.bool_, [None, None], 'truncations')
+        self._behaviour_log_probs_placeholder = Placeholder(np.float32, [None, None], 'behaviour_log_probs')
 
     def register_layers(self, layer_collection):
         raise NotImplementedError()

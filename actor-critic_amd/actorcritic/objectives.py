@@ -37,6 +37,12 @@ advantages and replaces the loss by PPO's clipped surrogate (acmi_ppo_loss); its
 ``optimize_shared`` op takes several epochs of minibatch gradient steps per
 ``session.run`` (:class:`PPOOptimizeOp`), over env slices of the batch or -- through a
 device row gather (acmi_gather_rows) -- over per-row shuffled minibatches.
+
+:class:`VTraceObjective` (beyond the reference as well) keeps A2C's losses and replaces the targets by
+V-trace's (acmi_vtrace; actorcritic/vtrace.py states them): importance weights of the current policy against
+the one that acted, ``model.behaviour_log_probs_placeholder`` or the batch's own forward, correct targets and
+advantages, so that its ``optimize_shared`` op may take several gradient steps per batch
+(:class:`VTraceOptimizeOp`, over env slices) and re-forms the targets at each.
 """
 
 from abc import ABCMeta, abstractmethod
@@ -127,13 +133,20 @@ class _Targets(Node):
         if obj._retnorm is not None:  # per-game reward scaling: once per run (this node is memoised)
             rewards = obj._retnorm.normalize(rewards, terminals, obj._gamma, st.reward_buffer(N, T), eng.stream(),
                                              eng.world_size)
-        tables = obj._tables(T, eng.device) if obj._gae_lambda is None else None
-        _ops.targets(rewards, terminals, fwd.flat_value, boot.flat_value, N, T, obj._gamma, obj._gae_lambda, tables,
-                     st.targets, st.adv, eng.stream(), truncated=trunc)
+        self._launch(ctx, st, fwd, boot, rewards, terminals, trunc)
         if obj._normalize:
             _normalize_advantages(eng, st.adv, N * T, obj._adv_eps)
         st.fwd = fwd
         return st
+
+    def _launch(self, ctx, st, fwd, boot, rewards, terminals, trunc):
+        """st.targets, st.adv <- the targets and advantages of the [N][T] batch."""
+        obj = self.objective
+        eng = obj._model.engine
+        N, T = fwd.batch, fwd.steps
+        tables = obj._tables(T, eng.device) if obj._gae_lambda is None else None
+        _ops.targets(rewards, terminals, fwd.flat_value, boot.flat_value, N, T, obj._gamma, obj._gae_lambda, tables,
+                     st.targets, st.adv, eng.stream(), truncated=trunc)
 
 
 class _ReturnStats(Node):
@@ -726,6 +739,241 @@ class PPOOptimizeOp(Node):
                 part = ForwardOut(eng, acts, rows, 1, obs)  # (a shuffled slice is not [env][step]-shaped)
                 st = self._step(ctx, run, part, sh.vecs, row0, rows, epoch, k)
         self.last_rows = order
+        return st
+
+
+class _VTraceBuffers(object):
+    def __init__(self, eng, M):
+        z = lambda: torch.zeros(M, dtype=torch.float32, device=eng.device)
+        self.behaviour_logp = z()  # the run's behaviour log-probabilities (the feed, or the batch's forward)
+        self.rho = z()  # the batch's clipped weights at the batch's forward
+        self.step_rho = z()  # a gradient step's, at the step's forward (row-aligned with the batch)
+
+
+class _VTraceRun(object):
+    """What one session.run shares between the V-trace nodes: the batch's per-row vectors (flat [N*T]) and
+    its two forwards; ``step_st`` is the update state of the last gradient step of a VTraceOptimizeOp."""
+
+    def __init__(self, fwd, boot, rewards, terminals, trunc, actions, masks, bufs):
+        self.fwd, self.boot = fwd, boot
+        self.rewards, self.terminals, self.trunc = rewards.reshape(-1), terminals.reshape(-1), trunc
+        if trunc is not None:
+            self.trunc = trunc.reshape(-1)
+        self.actions, self.masks, self.bufs = actions, masks, bufs
+        self.step_st = None
+
+
+class _VTraceTargets(_Targets):
+    """acmi_vtrace in place of acmi_returns / acmi_gae: targets, advantages and the clipped weights of the
+    batch at its forward, against the run's behaviour log-probabilities."""
+
+    def _launch(self, ctx, st, fwd, boot, rewards, terminals, trunc):
+        obj = self.objective
+        model = obj._model
+        eng = model.engine
+        M = fwd.M
+        actions = _device(ctx.eval(model.actions_placeholder), torch.int32, eng.device).reshape(-1)
+        if actions.numel() != M:
+            raise ValueError('actions must have the shape of the observations batch [env, step]')
+        bufs = obj._buffers.get(M)
+        if bufs is None:
+            bufs = obj._buffers[M] = _VTraceBuffers(eng, M)
+        masks = fwd.row_masks()
+        fed = ctx.feeds.get(model.behaviour_log_probs_placeholder)
+        if fed is not None:
+            fed = _device(fed, torch.float32, eng.device).reshape(-1)
+            if fed.numel() != M:
+                raise ValueError('behaviour log-probabilities must have the shape of the observations batch '
+                                 '[env, step]')
+            bufs.behaviour_logp.copy_(fed)
+        else:  # the batch's own forward acted (the rollout's cached activations), or stands in for what did
+            _ops.categorical(fwd.flat_logits, eng.A, M, eng.A, actions, None, bufs.behaviour_logp, eng.stream(),
+                             legal=masks)
+        run = st.vtrace = _VTraceRun(fwd, boot, rewards, terminals, trunc, actions, masks, bufs)
+        obj._launch_vtrace(run, fwd, boot, 0, fwd.batch, st, bufs.rho)
+        st.rho = bufs.rho
+
+
+class _VTraceLoss(_Loss):
+    """_Loss; once a VTraceOptimizeOp has stepped in the run, the scalars of its last gradient step."""
+
+    def _stepped(self, ctx):
+        return ctx.eval(self.objective._targets_node).vtrace.step_st
+
+    def _eval(self, ctx):
+        st = self._stepped(ctx)
+        return st.loss if st is not None else super()._eval(ctx)
+
+    def scalars(self, ctx):
+        st = self._stepped(ctx)
+        if st is not None:  # (all-reduced with the gradients: global means)
+            return st.loss[:3]
+        return super().scalars(ctx)
+
+
+class VTraceObjective(A2CObjective):
+    """A2C's losses on V-trace targets (Espeholt et al. 2018, IMPALA), beyond the reference: the actor-critic
+    objective for data that the policy being updated did not collect -- several passes over one batch, actors
+    whose parameters lag the learner, batches handed in from outside.  actorcritic/vtrace.py states the
+    recurrence; the clipped weight rho sits inside the advantage, so the loss, its gradient and every
+    optimizer are :class:`A2CObjective`'s (acmi_a2c_loss), K-FAC included for a single pass.
+
+    The behaviour policy's log-probabilities of the taken actions are fed through
+    ``model.behaviour_log_probs_placeholder`` [env, step]; unfed, the batch's own forward is the behaviour
+    policy (all weights 1 in a single pass: GAE(``gae_lambda``) targets, n-step returns at 1).
+    ``rho_bar >= c_bar > 0`` clip the weights of the temporal-difference terms and of the trace.
+    ``importance_weights`` is fetchable.  ``optimize_shared(num_epochs=, num_minibatches=)`` re-forms the
+    targets at every gradient step (:class:`VTraceOptimizeOp`)."""
+
+    def __init__(self, model, discount_factor=0.99, entropy_regularization_strength=0.01, gae_lambda=1.0,
+                 rho_bar=1.0, c_bar=1.0, normalize_advantages=False, normalize_returns=None, diagnostics=None,
+                 advantage_epsilon=1e-8, name=None):
+        if gae_lambda is None or not 0.0 <= float(gae_lambda) <= 1.0:
+            raise ValueError('gae_lambda must be in [0, 1], got {}'.format(gae_lambda))
+        if not float(rho_bar) > 0.0 or not float(c_bar) > 0.0:
+            raise ValueError('rho_bar and c_bar must be positive, got {} and {}'.format(rho_bar, c_bar))
+        if float(rho_bar) < float(c_bar):
+            raise ValueError('rho_bar ({}) must not be below c_bar ({})'.format(rho_bar, c_bar))
+        super().__init__(model, discount_factor, entropy_regularization_strength, name or 'VTraceObjective',
+                         gae_lambda=gae_lambda, normalize_advantages=normalize_advantages,
+                         advantage_epsilon=advantage_epsilon, normalize_returns=normalize_returns,
+                         diagnostics=diagnostics)
+        self._rho_bar, self._c_bar = float(rho_bar), float(c_bar)
+        self._buffers = {}
+        self._targets_node = _VTraceTargets(self)
+        self._loss_node = _VTraceLoss(self)
+        self._policy_loss = _LossScalar(self._loss_node, 0, 'policy_loss')
+        self._baseline_loss = _LossScalar(self._loss_node, 1, 'baseline_loss')
+        self._mean_entropy = _LossScalar(self._loss_node, 2, 'mean_entropy')
+
+    @property
+    def importance_weights(self):
+        """The clipped weights rho [env, step] of the batch at its forward (all ones unfed)."""
+        return _TargetView(self._targets_node, 'rho')
+
+    def _launch_vtrace(self, run, part, boot, env0, envs, st, rho):
+        """acmi_vtrace of the envs env0 .. env0+envs-1 of the run's batch: ``part`` and ``boot`` are forwards
+        of exactly those envs' rows and bootstrap observations; -> st.targets, st.adv and the rows' ``rho``."""
+        eng = self._model.engine
+        T = run.fwd.steps
+        sl = slice(env0 * T, (env0 + envs) * T)
+        _ops.vtrace(part.flat_logits, eng.A, eng.A, run.actions[sl], run.bufs.behaviour_logp[sl], run.rewards[sl],
+                    run.terminals[sl], part.flat_value, boot.flat_value, envs, T, self._gamma, self._gae_lambda,
+                    self._rho_bar, self._c_bar, st.targets, st.adv, rho[sl], eng.stream(),
+                    truncated=None if run.trunc is None else run.trunc[sl],
+                    legal=None if run.masks is None else run.masks[sl], bad_rows=eng._mask_bad_rows)
+
+    def optimize_shared(self, optimizer, baseline_loss_weight=0.5, num_epochs=1, num_minibatches=1, shuffle_seed=0,
+                        step_callback=None, global_step=None, **kwargs):
+        """``num_epochs = num_minibatches = 1`` (and no ``step_callback``, which the inherited op would not
+        call): :class:`A2CObjective`'s op (any optimizer).  Otherwise a
+        :class:`VTraceOptimizeOp`: per ``session.run``, ``num_epochs`` passes over the batch in
+        ``num_minibatches`` gradient steps each, over env slices (V-trace needs whole trajectories;
+        ``num_minibatches`` must divide the number of envs), first-order optimizers only."""
+        if int(num_epochs) < 1 or int(num_minibatches) < 1:
+            raise ValueError('num_epochs and num_minibatches must be at least 1')
+        if int(num_epochs) == 1 and int(num_minibatches) == 1 and step_callback is None:
+            if global_step is not None:
+                kwargs['global_step'] = global_step
+            return super().optimize_shared(optimizer, baseline_loss_weight, **kwargs)
+        from actorcritic.kfac_utils import KfacOptimizer
+        if isinstance(optimizer, KfacOptimizer):
+            raise NotImplementedError('VTraceObjective takes first-order optimizers only for several gradient '
+                                      'steps per batch: K-FAC runs the single pass (num_epochs = '
+                                      'num_minibatches = 1)')
+        if kwargs:
+            raise TypeError('unexpected arguments {}'.format(sorted(kwargs)))
+        self._vcoef = float(baseline_loss_weight)
+        return VTraceOptimizeOp(self, optimizer, int(num_epochs), int(num_minibatches), int(shuffle_seed),
+                                step_callback, global_step)
+
+
+class VTraceOptimizeOp(Node):
+    """Several V-trace gradient steps per ``session.run`` (multi-epoch A2C, an IMPALA-style learner):
+
+    1. the batch's forward (the rollout's cached activations, else a fresh one) and, once, the run's
+       behaviour log-probabilities (the feed, or that forward's), the scaled rewards (``normalize_returns``)
+       and the batch's targets (what ``target_values`` / ``importance_weights`` fetch, and the diagnostics);
+    2. for every epoch and every env slice, in the epoch's permuted order (:func:`ppo_minibatch_order`): the
+       tower on the slice's rows and on its bootstrap observations with the current parameters, acmi_vtrace
+       against the behaviour log-probabilities, the advantages normalised over the slice if asked,
+       acmi_a2c_loss, backward, all-reduce, the optimizer's kernel, ``step_callback(epoch, position)``;
+    3. ``global_step`` + 1 (once per run).
+
+    A slice is N / num_minibatches consecutive envs -- whole trajectories -- read in place.  ``last_order``
+    holds the slice order of the last run, ``[epoch][position] -> slice``.  The very first step of a run with
+    one minibatch re-uses the batch's two forwards.  With one minibatch a step's update state is the batch's:
+    ``target_values`` and ``advantage`` then hold the last step's."""
+    name = 'vtrace_optimize'
+
+    def __init__(self, objective, optimizer, num_epochs, num_minibatches, shuffle_seed, step_callback, global_step):
+        self.objective, self.optimizer = objective, optimizer
+        self.num_epochs, self.num_minibatches, self.shuffle_seed = num_epochs, num_minibatches, shuffle_seed
+        self.step_callback = step_callback
+        self.global_step = global_step
+        self.last_order = None
+        self._runs = 0
+
+    def _eval(self, ctx):
+        from actorcritic.envs.atari.model import ForwardOut
+        obj = self.objective
+        eng = obj._model.engine
+        batch_st = ctx.eval(obj._targets_node)
+        run = batch_st.vtrace
+        fwd, boot = run.fwd, run.boot
+        N, T, nmb = fwd.batch, fwd.steps, self.num_minibatches
+        step = self.global_step.value if self.global_step is not None else self._runs
+        slices = ppo_minibatch_rows(N, T, nmb)
+        order = ppo_minibatch_order(self.shuffle_seed, step, self.num_epochs, nmb)
+        diag = obj.diagnostics if obj.diagnostics is not None and obj.diagnostics.armed else None
+        if diag is not None:  # (as PPOOptimizeOp: of the whole op; the gradient is the last step's)
+            diag.before_update(eng, fwd, batch_st)
+        envs = N // nmb
+        st = None
+        for epoch, perm in enumerate(order):
+            for pos, j in enumerate(perm):
+                row0, rows = slices[j]
+                if st is None and nmb == 1:
+                    part, pboot = fwd, boot  # nothing has changed the parameters since the batch's forwards
+                else:
+                    acts = eng.activations(rows, 'vtrace')
+                    obs = fwd.obs[row0:row0 + rows]
+                    eng.forward(obs.data_ptr(), rows, acts.struct, want_value=True)
+                    part = ForwardOut(eng, acts, envs, T, obs)
+                    bacts = eng.activations(envs, 'vtrace_boot')
+                    bobs = boot.obs[j * envs:(j + 1) * envs]
+                    eng.forward(bobs.data_ptr(), envs, bacts.struct, want_value=True)
+                    pboot = ForwardOut(eng, bacts, envs, 1, bobs)
+                st = self._step(ctx, run, part, pboot, j * envs, envs, epoch, pos)
+        if diag is not None:
+            from actorcritic.nn import _innermost
+            diag.after_update(eng, fwd, st.grads, _innermost(self.optimizer))
+        run.step_st = st
+        self.last_order = order
+        self._runs += 1
+        if self.global_step is not None:
+            self.global_step.assign(self.global_step.value + 1)
+        return None
+
+    def _step(self, ctx, run, part, pboot, env0, envs, epoch, pos):
+        """One gradient step on the envs env0 .. env0+envs-1, forwarded as ``part`` / ``pboot``."""
+        obj, eng = self.objective, self.objective._model.engine
+        rows = part.M
+        st = eng.update_state(rows)
+        obj._launch_vtrace(run, part, pboot, env0, envs, st, run.bufs.step_rho)
+        if obj._normalize:
+            _normalize_advantages(eng, st.adv, rows, obj._adv_eps)
+        sl = slice(env0 * part.steps, env0 * part.steps + rows)
+        _ops.a2c_loss(part.flat_logits, eng.A, part.flat_value, run.actions[sl], st.targets, st.adv, rows, eng.A,
+                      float(obj._beta), float(obj._vcoef), 1.0 / eng.world_size, st.dhead, eng.ldh, st.loss_ws,
+                      st.loss, eng.stream(), legal=None if run.masks is None else run.masks[sl],
+                      bad_rows=eng._mask_bad_rows)
+        eng.backward(part, st, with_stats=False)
+        eng.allreduce(st, with_stats=False)
+        self.optimizer._apply_dense(ctx, eng, st.grads, 0.0)
+        eng.bump_version()
+        if self.step_callback is not None:
+            self.step_callback(epoch, pos)
         return st
 
 

@@ -155,6 +155,75 @@ __global__ void gae_kernel(const float* r, const uint8_t* d, const uint8_t* tr, 
 }
 
 // ---------------------------------------------------------------------------
+// V-trace targets (Espeholt et al. 2018; beyond the reference): GAE's scan with
+// clipped importance weights of the current policy against the behaviour policy.
+// A block covers E whole envs (E*T <= VTRACE_BLOCK when T allows it), two phases:
+//   1. one thread per (env, step) of the block's envs: log pi(a) by row_lse /
+//      row_logp (categorical_kernel's statements: the same bits), D = logp - blogp,
+//      w = expf(D), rho = min(rho_bar, w) -> rho[] (global), 0 where D is a NaN.
+//      c = min(c_bar, w) is min(c_bar, rho) because rho_bar >= c_bar: only rho travels.
+//   2. after one barrier, one thread per env: the reverse scan
+//        delta_t = rho_t ((r_t + (boot ? gamma V_{t+1} : 0)) - V_t)
+//        acc_t   = delta_t + (live ? ((gamma lambda) c_t) acc_{t+1} : 0)
+//        vs_t    = acc_t + V_t                                   -> targets
+//        nextv   = live ? vs_{t+1} : (truncated_t ? V_{t+1} : 0)
+//        adv_t   = rho_t ((r_t + gamma nextv) - V_t)
+//      (vs_T = V_T = v_boot; live / boot as gae_kernel) with the operation order fixed
+//      (__f*_rn), so vtrace_f32 (actorcritic/vtrace.py) restates it bit for bit and
+//      rho = c = 1 gives gae_kernel's targets.
+// The block reads only rho values that its own threads wrote: the barrier orders them.
+// ---------------------------------------------------------------------------
+constexpr int VTRACE_BLOCK = 256;
+
+template <bool MASKED, bool TRUNC>
+__global__ void __launch_bounds__(VTRACE_BLOCK)
+    vtrace_kernel(const float* logits, int ld, int A, const int32_t* actions, const float* blogp, const float* r,
+                  const uint8_t* d, const uint8_t* tr, const float* v, const float* vb, int N, int T, int E,
+                  float gamma, float gl, float rho_bar, float c_bar, const uint32_t* legal, int32_t* bad_rows,
+                  float* tgt, float* adv, float* rho, float* logp_out) {
+  const int n0 = blockIdx.x * E;  // (the grid is cdiv(N, E) blocks: n0 < N)
+  const int envs = N - n0 < E ? N - n0 : E;
+  const long long row0 = (long long)n0 * T;
+  const int rows = envs * T;  // (<= VTRACE_BLOCK, or one env's T)
+  for (int k = threadIdx.x; k < rows; k += VTRACE_BLOCK) {
+    const long long m = row0 + k;
+    const float* z = logits + m * ld;
+    const uint32_t lg = MASKED ? legal_bits(legal[m], A) : 0xFFFFFFFFu;
+    const RowLse lse = row_lse<MASKED>(z, A, lg);
+    const int act = actions[m];
+    const bool ok = action_ok<MASKED>(lg, act, A);
+    const float lp = ok ? row_logp(z[act], lse) : -INFINITY;
+    if (!ok && bad_rows) atomicAdd(bad_rows, 1);
+    const float w = expf(__fsub_rn(lp, blogp[m]));
+    // a NaN (by its bits: both log-probabilities -inf, or a NaN logit) weighs nothing
+    const bool nan = (__float_as_uint(w) & 0x7fffffffu) > 0x7f800000u;
+    rho[m] = nan ? 0.f : fminf(rho_bar, w);
+    if (logp_out) logp_out[m] = lp;
+  }
+  __syncthreads();
+  if ((int)threadIdx.x >= envs) return;
+  const int n = n0 + threadIdx.x;
+  float next_v = vb[n], next_vs = vb[n], acc = 0.f;
+  for (int t = T - 1; t >= 0; --t) {
+    const long long i = (long long)n * T + t;
+    const bool live = d[i] == 0;
+    bool trunc = false;
+    if (TRUNC) trunc = !live && tr[i] != 0;
+    const bool boot = live || trunc;
+    const float vi = v[i], ri = r[i], rh = rho[i];
+    const float c = fminf(c_bar, rh);
+    const float delta = __fmul_rn(rh, __fsub_rn(__fadd_rn(ri, boot ? __fmul_rn(gamma, next_v) : 0.f), vi));
+    acc = __fadd_rn(delta, live ? __fmul_rn(__fmul_rn(gl, c), acc) : 0.f);
+    const float vs = __fadd_rn(acc, vi);
+    const float nextv = live ? next_vs : (trunc ? next_v : 0.f);
+    adv[i] = __fmul_rn(rh, __fsub_rn(__fadd_rn(ri, __fmul_rn(gamma, nextv)), vi));
+    tgt[i] = vs;
+    next_v = vi;
+    next_vs = vs;
+  }
+}
+
+// ---------------------------------------------------------------------------
 // advantage normalisation (an option beyond the reference): batch moments in
 // double, two fixed-order passes; normalise with the (all-reduced) moments
 // ---------------------------------------------------------------------------
@@ -883,6 +952,34 @@ int acmi_gae_trunc(const float* rewards, const uint8_t* terminals, const uint8_t
   ACMI_REQUIRE(truncated, ACMI_ERR_ARG, "acmi_gae_trunc: bad arguments");
   return gae_launch("acmi_gae_trunc", rewards, terminals, truncated, values, v_boot, N, T, gamma, lambda, targets,
                     adv, stream);
+}
+
+int acmi_vtrace(const float* logits, int ld, int A, const int32_t* actions, const float* behaviour_logp,
+                const float* rewards, const uint8_t* terminals, const uint8_t* truncated, const float* values,
+                const float* v_boot, int N, int T, float gamma, float lambda, float rho_bar, float c_bar,
+                const uint32_t* legal, int32_t* bad_rows, float* targets, float* adv, float* rho, float* log_prob,
+                acmi_stream_t stream) {
+  ACMI_REQUIRE(logits && actions && behaviour_logp && rewards && terminals && values && v_boot && targets && adv &&
+                   rho,
+               ACMI_ERR_ARG, "acmi_vtrace: a required pointer is NULL");
+  ACMI_REQUIRE(N >= 0 && T >= 0 && A >= 1 && ld >= A && (long long)N * T <= INT32_MAX, ACMI_ERR_ARG,
+               "acmi_vtrace: N=%d, T=%d must not be negative (N*T below 2^31), A=%d at least 1 and ld=%d at least A",
+               N, T, A, ld);
+  ACMI_REQUIRE(!legal || A <= 32, ACMI_ERR_ARG, "acmi_vtrace: num_actions=%d, a legal-action mask holds at most 32",
+               A);
+  // (written so that a NaN fails each of them)
+  ACMI_REQUIRE(lambda >= 0.f && lambda <= 1.f && c_bar > 0.f && rho_bar >= c_bar, ACMI_ERR_ARG,
+               "acmi_vtrace: lambda=%g outside [0, 1], c_bar=%g not positive or rho_bar=%g below c_bar",
+               (double)lambda, (double)c_bar, (double)rho_bar);
+  if (N == 0 || T == 0) return ACMI_OK;
+  const int E = T < VTRACE_BLOCK ? VTRACE_BLOCK / T : 1;  // whole envs per block
+  const auto kern = legal ? (truncated ? vtrace_kernel<true, true> : vtrace_kernel<true, false>)
+                          : (truncated ? vtrace_kernel<false, true> : vtrace_kernel<false, false>);
+  hipLaunchKernelGGL(kern, dim3(cdiv(N, E)), dim3(VTRACE_BLOCK), 0, (hipStream_t)stream, logits, ld, A, actions,
+                     behaviour_logp, rewards, terminals, truncated, values, v_boot, N, T, E, gamma, gamma * lambda,
+                     rho_bar, c_bar, legal, bad_rows, targets, adv, rho, log_prob);
+  ACMI_LAUNCH_CHECK("acmi_vtrace");
+  return ACMI_OK;
 }
 
 int64_t acmi_adv_moments_ws_doubles(int64_t M) { (void)M; return 2LL * MOM_BLOCKS; }

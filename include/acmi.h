@@ -287,6 +287,42 @@ int acmi_gae_trunc(const float* rewards, const uint8_t* terminals,
                    int N, int T, float gamma, float lambda, float* targets,
                    float* adv, acmi_stream_t stream);
 
+/* V-trace targets and advantages (Espeholt et al. 2018, IMPALA) -- beyond the
+ * reference: acmi_gae_trunc's scan with clipped importance weights, for data
+ * that the policy being updated did not collect (several passes over a batch,
+ * lagging actors).  One launch; batch-major [N][T] rows m = n*T + t.
+ *   logits [N*T][ld], actions: the CURRENT policy and the taken actions;
+ *   behaviour_logp[N*T]: log mu(a) of the policy that acted;
+ *   truncated: nullable (NULL: every terminal cuts the bootstrap);
+ *   legal, bad_rows: nullable, as the *_masked entry points take them (A <= 32
+ *   with legal; log pi of an action outside the row's set is -INFINITY and the
+ *   row counts in *bad_rows).
+ * Per row, f32: logp = acmi_categorical's log_prob (the same statements, the
+ * same bits), D = logp - behaviour_logp, w = expf(D),
+ *   rho = min(rho_bar, w), c = min(c_bar, w);
+ *   D = +inf: the bars; D = -inf: 0; D a NaN (both log-probabilities -inf):
+ *   rho = c = 0 -- the row contributes nothing.
+ * Per env, in reverse, with vs_T = V_T = v_boot, live = d_t == 0,
+ * boot = live || truncated_t (the chain is cut at every terminal):
+ *   delta_t = rho_t * ((r_t + (boot ? gamma*V_{t+1} : 0)) - V_t)
+ *   acc_t   = delta_t + (live ? ((gamma*lambda) * c_t) * acc_{t+1} : 0)
+ *   targets = vs_t = acc_t + V_t
+ *   nextv   = live ? vs_{t+1} : (truncated_t ? V_{t+1} : 0)
+ *   adv_t   = rho_t * ((r_t + gamma*nextv) - V_t)
+ * float32, no contraction, in exactly that order (actorcritic/vtrace.py
+ * restates it); gamma*lambda is formed as acmi_gae forms it, so rho = c = 1
+ * (behaviour_logp = logp, bars >= 1) gives the bytes of acmi_gae /
+ * acmi_gae_trunc's targets.  Outputs: targets, adv, rho (the clipped rho),
+ * each [N*T], and log_prob (nullable) = logp.  0 <= lambda <= 1, c_bar > 0,
+ * rho_bar >= c_bar, N, T >= 0 (N*T == 0: ACMI_OK, nothing enqueued). */
+int acmi_vtrace(const float* logits, int ld, int A, const int32_t* actions,
+                const float* behaviour_logp, const float* rewards,
+                const uint8_t* terminals, const uint8_t* truncated,
+                const float* values, const float* v_boot, int N, int T, float gamma,
+                float lambda, float rho_bar, float c_bar, const uint32_t* legal,
+                int32_t* bad_rows, float* targets, float* adv, float* rho,
+                float* log_prob, acmi_stream_t stream);
+
 /* Advantage normalisation (an option beyond the reference, which has none,
  * objectives.py:128-130): moments[0..1] = (sum, sum of squares) of adv[0..M)
  * in double, fixed order (ws: acmi_adv_moments_ws_doubles(M) doubles).  A

@@ -1,12 +1,15 @@
 #!/usr/bin/env python
 """Learning curves on the device games.  Needs a GPU.
 
-Trains A2C, ACKTR or PPO (the examples' settings) on Catch or Breakout from a seed and,
+Trains A2C, ACKTR, PPO or the V-trace actor-critic (the examples' settings) on Catch or Breakout from a seed and,
 every --every updates, plays a separate batch of envs with the greedy policy
 (envs.games.evaluate): one JSON line per point with the env-steps so far and the mean
 return, after a first line with the uniform policy's.  The lines also go to --out.
 
     python scripts/learn_games.py --algo a2c --game catch --updates 2000 --every 250 --seeds 1 2 3
+
+--algo vtrace takes --epochs E --minibatches K (gradient steps per batch: E passes over K env slices; 1 x 1 is
+A2C's update), --rho-bar, --c-bar and --lambda (examples/atari/vtrace.py).
 
 --episodic-life and --max-episode-steps N train under those rules (DeviceGameEnvs); the
 evaluation envs never take episodic life (evaluate counts terminals as finished games), so
@@ -57,7 +60,9 @@ def run(args, seed, emit):
     torch.cuda.set_device(0)
     sess.reset_default_graph()
     N, T, E = args.envs, args.steps, args.episodes
-    head = dict(algo=args.algo, game=args.game, seed=seed, envs=N, steps=T, eval_envs=args.eval_envs, eval_episodes=E,
+    vt = dict(epochs=args.epochs, minibatches=args.minibatches, rho_bar=args.rho_bar, c_bar=args.c_bar,
+              gae_lambda=args.gae_lambda) if args.algo == 'vtrace' else {}
+    head = dict(algo=args.algo, **vt, game=args.game, seed=seed, envs=N, steps=T, eval_envs=args.eval_envs, eval_episodes=E,
                 episodic_life=args.episodic_life, max_episode_steps=args.max_episode_steps,
                 mask_actions=args.mask_actions, normalize_returns=args.normalize_returns,
                 **(dict(episode_stats=True) if args.episode_stats else {}))
@@ -147,17 +152,26 @@ def run(args, seed, emit):
                   diagnostics=diag or False, **rules, **fused, **keep)
     if args.algo == 'ppo':
         train_ppo(args.game, N, T, ckpt_dir, args.game, **kwargs)
+    elif args.algo == 'vtrace':
+        from actorcritic.examples.atari.vtrace import train_vtrace
+        train_vtrace(args.game, N, T, ckpt_dir, args.game, num_epochs=args.epochs, num_minibatches=args.minibatches,
+                     rho_bar=args.rho_bar, c_bar=args.c_bar, gae_lambda=args.gae_lambda, **kwargs)
     else:
         train_a2c_acktr(args.algo == 'acktr', args.game, N, T, ckpt_dir, args.game, **kwargs)
 
 
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument('--algo', choices=('a2c', 'acktr', 'ppo'), default='a2c')
+    ap.add_argument('--algo', choices=('a2c', 'acktr', 'ppo', 'vtrace'), default='a2c')
     ap.add_argument('--game', choices=('catch', 'breakout', 'catch+breakout'), default='catch')
     ap.add_argument('--envs', type=int, default=32)
     ap.add_argument('--steps', type=int, default=None, help='rollout length (default: a2c 5, acktr 20, ppo 128)')
     ap.add_argument('--updates', type=int, default=2000)
+    ap.add_argument('--epochs', type=int, default=1, help='vtrace: passes over a batch')
+    ap.add_argument('--minibatches', type=int, default=1, help='vtrace: env slices (gradient steps) per pass')
+    ap.add_argument('--rho-bar', type=float, default=1.0, help='vtrace: clip of the TD terms\' importance weights')
+    ap.add_argument('--c-bar', type=float, default=1.0, help='vtrace: clip of the trace\'s importance weights')
+    ap.add_argument('--lambda', dest='gae_lambda', type=float, default=1.0, help='vtrace: lambda in [0, 1]')
     ap.add_argument('--every', type=int, default=250)
     ap.add_argument('--seeds', type=int, nargs='+', default=[1])
     ap.add_argument('--eval-envs', type=int, default=32)
@@ -188,7 +202,7 @@ def main():
     if args.run_state and not args.checkpoint_dir:
         ap.error('--run-state needs --checkpoint-dir')
     if args.steps is None:
-        args.steps = {'a2c': 5, 'acktr': 20, 'ppo': 128}[args.algo]  # the examples' rollout lengths
+        args.steps = {'a2c': 5, 'acktr': 20, 'ppo': 128, 'vtrace': 5}[args.algo]  # the examples' rollout lengths
     out = open(args.out, 'a') if args.out else None
 
     def emit(rec):
