@@ -624,7 +624,10 @@ int conv1_afactor_u8(const uint8_t* obs, long long img_stride, int B, float* ast
     af_plan(rows, &nchunk, &chunk);
   ACMI_REQUIRE(conv1_afactor_ws_ints(rows) <= ws_ints, ACMI_ERR_WS,
                "conv1 A-factor workspace too small");
-  ACMI_REQUIRE(img_stride % 8 == 0, ACMI_ERR_ARG, "conv1 A factor needs 8-byte aligned images");
+  // internal guard: the public entry points refuse this before their first launch
+  // (check_update_args, backward.hpp), so no call gets here with d1..d4 written
+  ACMI_REQUIRE(img_stride % 8 == 0 && (uintptr_t)obs % 8 == 0, ACMI_ERR_ARG,
+               "conv1 A factor needs 8-byte aligned images");
   ACMI_REQUIRE(img_stride > 0 && (long long)B * img_stride < (1LL << 32), ACMI_ERR_ARG,
                "conv1 A factor: frames must span < 2^32 bytes");
   int* part = ws;

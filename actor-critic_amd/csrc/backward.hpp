@@ -37,6 +37,8 @@ struct UpdateArgs {
   bool nonnull;
   const acmi_acts_t* masks;
   bool with_obs;
+  const uint8_t* obs;
+  bool obs8;  // conv1's A factor runs (a_stats): 8-byte patch loads (afactor_u8.hip)
   long long img_stride;
   const acmi_bwd_t* bwd;
   bool distinct;  // acmi_backward_stacked: the two chains' buffers differ
@@ -51,6 +53,12 @@ static int check_update_args(const acmi_net_t* net, int B, const UpdateArgs& u, 
   if (u.with_obs) {
     ACMI_REQUIRE(B > 0 && u.img_stride >= 84 * 84 * 4 && u.img_stride % 4 == 0, ACMI_ERR_ARG,
                  "%s: bad B / img_stride", u.fn);
+    // the widest load from obs: uint32 (conv1's weight gradient from the u8 patches,
+    // ConvRows<uint8_t>::stage), 8 bytes with the conv1 A factor
+    const int al = u.obs8 ? 8 : 4;
+    ACMI_REQUIRE((uintptr_t)u.obs % al == 0 && u.img_stride % al == 0, ACMI_ERR_ARG,
+                 "%s: obs and img_stride must be multiples of %d bytes%s", u.fn, al,
+                 u.obs8 ? " (with a_stats: the conv1 A factor loads 8 bytes)" : "");
     ACMI_REQUIRE(u.bwd->ldh >= net->num_actions + 1 && u.bwd->ldh % 4 == 0, ACMI_ERR_ARG,
                  "%s: ldh must be >= A+1 and a multiple of 4 (zero padded)", u.fn);
     ACMI_REQUIRE(spans32(B, u.img_stride, 84 * 84 * 4) && spans32(B, 400 * 32, 400 * 32), ACMI_ERR_ARG,

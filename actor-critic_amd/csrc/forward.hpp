@@ -485,7 +485,8 @@ template <int C3, class Env = SynthEnv>
 static int forward_impl(const Layout& L, const float* P, const uint8_t* obs,
                         long long img_stride, int B, const acmi_acts_t* a,
                         int want_value, long long act_img_stride,
-                        hipStream_t s, const typename Env::Args* tail = nullptr, const void* prep = nullptr) {
+                        hipStream_t s, const typename Env::Args* tail = nullptr, const void* prep = nullptr,
+                        const char* fn = "acmi_forward") {
   // act_img_stride: images between consecutive batch rows in the activation
   // buffers (1 = contiguous; T = rollout step t of an env-major buffer).
   const long long st = act_img_stride;
@@ -495,8 +496,9 @@ static int forward_impl(const Layout& L, const float* P, const uint8_t* obs,
   const bool tower =
       g_gemm_mode == ACMI_GEMM_X3 && prep && (uintptr_t)obs % 16 == 0 && img_stride % 16 == 0;
   ACMI_REQUIRE(tower || g_forward_mode == ACMI_FWD_F32, ACMI_ERR_ARG,
-               "16-bit forward needs the fused tower: net->conv_prep and 16-byte aligned observations / image "
-               "stride");
+               "%s: the 16-bit forward needs the fused tower: net->conv_prep and 16-byte aligned observations / "
+               "image stride",
+               fn);
   // step fusion (acmi_rollout_io_t): this step's tower ran in the previous
   // step's tail; the next step's tower runs in this step's tail
   const bool tower_done = tail && tail->io.tower_done;
@@ -650,25 +652,29 @@ template <class Env = SynthEnv>
 static int forward_dispatch(const acmi_net_t* net, const uint8_t* obs, int64_t img_stride,
                             int B, const acmi_acts_t* acts, int want_value,
                             long long act_stride, acmi_stream_t stream,
-                            const typename Env::Args* tail = nullptr) {
+                            const typename Env::Args* tail = nullptr, const char* fn = "acmi_forward") {
+  // fn: the entry point's name, in every message.  Every argument error comes
+  // before anything is enqueued (forward_impl's own are ahead of its launches).
   Layout L;
-  ACMI_REQUIRE(net && acts && obs && net->params, ACMI_ERR_ARG, "acmi_forward: null argument");
+  ACMI_REQUIRE(net && acts && obs && net->params, ACMI_ERR_ARG, "%s: null argument", fn);
   ACMI_REQUIRE(make_layout(net->num_actions, net->conv3_filters, &L), ACMI_ERR_ARG,
-               "acmi_forward: bad A=%d/C3=%d", net->num_actions, net->conv3_filters);
+               "%s: bad A=%d/C3=%d", fn, net->num_actions, net->conv3_filters);
   ACMI_REQUIRE(B >= 0 && img_stride >= 84 * 84 * 4 && img_stride % 4 == 0, ACMI_ERR_ARG,
-               "acmi_forward: bad B=%d / img_stride=%lld", B, (long long)img_stride);
+               "%s: bad B=%d / img_stride=%lld (>= 28224, a multiple of 4)", fn, B, (long long)img_stride);
+  // the per-layer conv1 loads patch pixels as uint32 (ConvRows<uint8_t>::stage)
+  ACMI_REQUIRE((uintptr_t)obs % 4 == 0, ACMI_ERR_ARG, "%s: obs must be 4-byte aligned", fn);
   ACMI_REQUIRE(acts->a1 && acts->a2 && acts->a3 && acts->a4 && acts->logits &&
                    acts->ld_logits >= net->num_actions && (!want_value || acts->value),
-               ACMI_ERR_ARG, "acmi_forward: bad activation buffers");
-  ACMI_REQUIRE(masks_ok(acts), ACMI_ERR_ARG, "acmi_forward: ReLU masks m1..m3 must be all set or all NULL");
-  ACMI_REQUIRE(act_stride >= 1, ACMI_ERR_ARG, "bad activation stride");
+               ACMI_ERR_ARG, "%s: bad activation buffers", fn);
+  ACMI_REQUIRE(masks_ok(acts), ACMI_ERR_ARG, "%s: ReLU masks m1..m3 must be all set or all NULL", fn);
+  ACMI_REQUIRE(act_stride >= 1, ACMI_ERR_ARG, "%s: bad activation stride", fn);
   ACMI_REQUIRE(spans32(B, img_stride, 84 * 84 * 4) && spans32(B, act_stride * 400 * 32, 400 * 32),
-               ACMI_ERR_ARG, "acmi_forward: batch spans >= 2^31 elements (B=%d)", B);
+               ACMI_ERR_ARG, "%s: batch spans >= 2^31 elements (B=%d)", fn, B);
   if (B == 0) return ACMI_OK;
   hipStream_t s = (hipStream_t)stream;
   return dispatch_c3(L.C3, [&](auto c3) {
     return forward_impl<decltype(c3)::value, Env>(L, net->params, obs, img_stride, B, acts, want_value, act_stride, s,
-                                                  tail, net->conv_prep);
+                                                  tail, net->conv_prep, fn);
   });
 }
 

@@ -363,7 +363,8 @@ int acmi_forward_strided(const acmi_net_t* net, const uint8_t* obs, int64_t img_
                          acmi_stream_t stream) {
   ACMI_REQUIRE(net_modes_ok(net), ACMI_ERR_ARG, "acmi_forward_strided: bad acmi_net_t mode fields");
   const ModeScope mode_scope(net);
-  return forward_dispatch(net, obs, img_stride, B, acts, want_value, act_img_stride, stream);
+  return forward_dispatch(net, obs, img_stride, B, acts, want_value, act_img_stride, stream, nullptr,
+                          "acmi_forward_strided");
 }
 
 // acmi_rollout_step / acmi_rollout_step_masked (legal: nullptr / one word per env)
@@ -457,7 +458,8 @@ int acmi_backward(const acmi_net_t* net, const uint8_t* obs, int64_t img_stride,
                   float* a_stats, float* ws, int64_t ws_floats, acmi_stream_t stream) {
   Layout L;
   const UpdateArgs u{"acmi_backward", /*nonnull*/ acts && bwd && grads && ws && obs, /*masks*/ acts,
-                     /*with_obs*/ true, img_stride, bwd, /*distinct*/ true, {ws_floats, ws_floats}};
+                     /*with_obs*/ true, obs, /*obs8*/ a_stats != nullptr, img_stride, bwd, /*distinct*/ true,
+                     {ws_floats, ws_floats}};
   const int rc = check_update_args(net, B, u, &L);
   if (rc) return rc;
   const ModeScope mode_scope(net);
@@ -477,8 +479,8 @@ int acmi_backward_stacked(const acmi_net_t* net, const uint8_t* obs, int64_t img
   const bool nonnull = acts && bwd && bwd_s && grads && a_stats && ws && ws_s && obs;
   const bool distinct = nonnull && ws != ws_s && bwd->d1 != bwd_s->d1 && bwd->d2 != bwd_s->d2 &&
                         bwd->d3 != bwd_s->d3 && bwd->d4 != bwd_s->d4;
-  const UpdateArgs u{"acmi_backward_stacked", nonnull, /*masks*/ acts, /*with_obs*/ true, img_stride, bwd, distinct,
-                     {ws_floats, ws_s_floats}};
+  const UpdateArgs u{"acmi_backward_stacked", nonnull, /*masks*/ acts, /*with_obs*/ true, obs, /*obs8*/ true,
+                     img_stride, bwd, distinct, {ws_floats, ws_s_floats}};
   const int rc = check_update_args(net, B, u, &L);
   if (rc) return rc;
   const ModeScope mode_scope(net);
@@ -494,7 +496,7 @@ int acmi_kfac_output_stats_finish(const acmi_net_t* net, int B, const acmi_acts_
                                   float* g_stats, float* ws_s, int64_t ws_s_floats, acmi_stream_t stream) {
   Layout L;
   const UpdateArgs u{"acmi_kfac_output_stats_finish", /*nonnull*/ acts && bwd_s && g_stats && ws_s, /*masks*/ nullptr,
-                     /*with_obs*/ false, 0, nullptr, /*distinct*/ true, {ws_s_floats, ws_s_floats}};
+                     /*with_obs*/ false, nullptr, false, 0, nullptr, /*distinct*/ true, {ws_s_floats, ws_s_floats}};
   const int rc = check_update_args(net, B, u, &L);
   if (rc) return rc;
   const ModeScope mode_scope(net);
@@ -516,8 +518,8 @@ static int output_stats_entry(const char* fn, const acmi_net_t* net, int B, cons
                               uint32_t counter, float* g_stats, float* ws, int64_t ws_floats,
                               const uint32_t* legal, acmi_stream_t stream) {
   Layout L;
-  const UpdateArgs u{fn, /*nonnull*/ acts && bwd && g_stats && ws, /*masks*/ acts, /*with_obs*/ false, 0, nullptr,
-                     /*distinct*/ true, {ws_floats, ws_floats}};
+  const UpdateArgs u{fn, /*nonnull*/ acts && bwd && g_stats && ws, /*masks*/ acts, /*with_obs*/ false, nullptr, false,
+                     0, nullptr, /*distinct*/ true, {ws_floats, ws_floats}};
   const int rc = check_update_args(net, B, u, &L);
   if (rc) return rc;
   const ModeScope mode_scope(net);

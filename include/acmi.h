@@ -171,6 +171,20 @@ int acmi_kfac_layout(int num_actions, int conv3_filters, int64_t* din6,
  * ReLU, policy logits and value heads.  `obs` holds B NHWC u8 images
  * [84][84][4]; image b starts at obs + b*img_stride (bytes), which lets the
  * rollout read step t of a [N][T][84][84][4] buffer in place.
+ *
+ * Addressing (acmi_forward, acmi_forward_strided; every violation is
+ * ACMI_ERR_ARG before anything is enqueued):
+ *   - img_stride >= 28224, obs and img_stride multiples of 4 (the per-layer
+ *     conv1 loads a pixel's 4 channels as one uint32);
+ *   - the fused conv tower (net->conv_prep, ACMI_GEMM_X3) loads 16 bytes: it
+ *     runs only when obs and img_stride are multiples of 16, the per-layer
+ *     kernels otherwise (f32-class either way, not bit-identical to each
+ *     other).  ACMI_FWD_BF16 exists only in the tower and is refused otherwise;
+ *   - ld_logits >= num_actions (columns past num_actions are not written),
+ *     value non-NULL unless want_value == 0 (then it is not written);
+ *   - 32-bit offsets: (B - 1) * img_stride + 28224 < 2^31 and
+ *     (B - 1) * act_img_stride * 12800 + 12800 < 2^31 (a1's floats);
+ *   - B == 0 is ACMI_OK and writes nothing.
  * ---------------------------------------------------------------------- */
 typedef struct acmi_acts {
   float* a1;     /* [B][20][20][32] post-ReLU                               */
@@ -553,6 +567,14 @@ int acmi_gather_rows(const uint8_t* obs, int64_t img_stride, int64_t src_rows,
  * dhead: [B][ldh] from acmi_a2c_loss, ldh >= A+1 and a multiple of 4 (rows
  * are read as float4; padding columns zero), else ACMI_ERR_ARG before anything
  * is enqueued.  d1..d4 are [B]x(layer output) scratch.
+ * obs: image b at obs + b*img_stride as for acmi_forward, B >= 1,
+ * img_stride >= 28224, (B - 1) * img_stride + 28224 < 2^31.  Alignment, by the
+ * widest load made from obs: without statistics (acmi_backward, a_stats ==
+ * NULL) obs and img_stride multiples of 4, as the forward (conv1's weight
+ * gradient reads uint32 pixels); with statistics (a_stats != NULL, and
+ * acmi_backward_stacked always) multiples of 8 (conv1's A factor reads two
+ * pixels per load).  Every violation is ACMI_ERR_ARG before anything is
+ * enqueued (nothing is written).
  * ws: ws_floats >= acmi_backward_ws_floats(B, A, C3) floats; a smaller
  * ws_floats fails with ACMI_ERR_WS before anything is enqueued (nothing is
  * written).  Layout: [operand-scale scratch | conv1 A-factor integers |
@@ -916,7 +938,10 @@ int acmi_atari_plan(int H, int W, int32_t out[6]);
 /* Rollout variant of acmi_forward: batch row b reads image b of `obs` and
  * writes activation row b*act_img_stride (env-major [N][T] buffers, the
  * pointers in *acts pre-offset by step t), so step t of a T-step rollout
- * lands where the update expects it and the update re-uses it. */
+ * lands where the update expects it and the update re-uses it: a1..a4, value
+ * and m1..m3 at b*act_img_stride rows of their own row size, logits at
+ * b*act_img_stride*ld_logits floats; the rows in between are not touched.
+ * act_img_stride >= 1; obs / img_stride / ld_logits as for acmi_forward. */
 int acmi_forward_strided(const acmi_net_t* net, const uint8_t* obs,
                          int64_t img_stride, int B, const acmi_acts_t* acts,
                          int want_value, int64_t act_img_stride,
